@@ -2,10 +2,18 @@
 """Headline benchmark: SConformerXL training step (forward + CTC + backward + clip + MADGRAD [+ RCCL gradient
 all-reduce]) on synthetic mel, BASELINE.json config 3: 6L/768D/6H rotary theta=1.5M, seq=16384, bf16 compute.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0): metric = spectrogram-frames/sec (whole job), plus
+Prints ONE JSON line (rank 0): metric = spectrogram-frames/sec (whole job), ms_per_step = wall time of one of the K timed
+steps.  A plain run sets up, warms up, times the K steps and prints that line, nothing else.
+  --dump-outputs DIR : after the timed steps, write what the last timed step handed back (the summed CTC loss) and the model
+                 state it left (parameters after the MADGRAD update, BatchRenorm buffers; tensors above an equal share of
+                 DUMP_ELEMENTS as a fixed seeded sample) as DIR/<name>.npy, f32 / f64.  Inputs are seeded and every
+                 reduction of the step runs in a fixed order, so runs with the same arguments write the same arrays and
+                 two builds can be compared output for output.
+  --full       : everything below as well (off by default).  The roofline's HIP events sit inside the timed region, so a
+                 --full run's ms_per_step carries their cost.
   roofline     : the dominant kernel (NT bf16 MFMA GEMM) timed live with HIP events on its stream over the timed region,
                  algorithmic FLOPs = 2*M*N*K per launch, peak = 2.5 PFLOP/s dense bf16;
                  roofline.attention = the attention forward / backward launches of the same timed region against the same peak
@@ -15,8 +23,8 @@ Prints ONE JSON line (rank 0): metric = spectrogram-frames/sec (whole job), plus
                  workload (N=1, rank 0 only); cpu_baseline_t1024: the same for the 1024-frame context;
   sweep        : (N=1, after the timed region of the headline) the other north-star contexts through the same code, each at its
                  configured batch: c2 (T=1024), c4 (9L, T=16384, per-layer checkpointing), c5 (3L/2048D, T=131072);
-  dist         : (N>1) backend, gradient bytes all-reduced per step and rank, and how long the step's stream waited for the
-                 all-reduces it could not hide behind the backward.
+  dist         : (N>1) backend, gradient bytes all-reduced per step and rank, and (--full) how long the step's stream waited
+                 for the all-reduces it could not hide behind the backward.
 """
 import argparse
 import json
@@ -67,6 +75,7 @@ CONFIGS = {
 }
 PEAK_BF16_DENSE = 2.5e15        # MI355X_MICROARCH.md: ~2.5 PFLOP/s dense bf16 MFMA
 PEAK_HBM = 8.0e12               # MI355X_MICROARCH.md: 8.0 TB/s HBM3E (spec; 6.3 TB/s is what a copy reaches)
+DUMP_ELEMENTS = 8 << 20         # --dump-outputs: elements across all state tensors (32 MiB of f32)
 
 
 GEMM_KERNELS = {0: 'gemm_kernel<NT> (128x128 tile)',
@@ -338,6 +347,33 @@ def run_config(name: str, steps: int, warmup: int, batch: int = 0) -> dict:
     return out
 
 
+def dump_outputs(out_dir: str, results: dict, model) -> int:
+    """--dump-outputs: results {name: tensor} and the model's state_dict as out_dir/<name>.npy (state tensors as
+    state.<key>.npy), f64 tensors and integer buffers as f64, everything else as f32.  A state tensor with more elements than
+    DUMP_ELEMENTS / (number of state tensors) is written as that many elements at fixed positions of its flattened form (a
+    permutation from a generator seeded with the tensor's index in the state_dict, sorted): the same positions in every run.
+    Returns the bytes written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sd = model.state_dict()
+    cap = max(1, DUMP_ELEMENTS // max(len(sd), 1))
+    arrays = dict(results)
+    for i, (k, v) in enumerate(sd.items()):
+        v = v.detach().reshape(-1)
+        if v.numel() > cap:
+            g = torch.Generator().manual_seed(1000 + i)
+            idx = torch.randperm(v.numel(), generator=g)[:cap].sort().values
+            v = v[idx.to(v.device)]
+        arrays['state.' + k] = v
+    total = 0
+    for name, v in arrays.items():
+        v = v.detach().cpu()
+        a = v.double().numpy() if v.dtype == torch.float64 or not v.is_floating_point() else v.float().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+    return total
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as a CHILD `torch.distributed.run` - before this
     process has touched the GPU, and never by exec - relay its output (rank 0 prints the JSON line) and return its exit code."""
@@ -362,8 +398,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='c3', choices=list(CONFIGS))
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch (default: config value)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-sweep', action='store_true', help='skip the c2 / c4 / c5 lines after the headline (N=1, c3 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline (HIP events in the timed region), the CPU baselines with CTC parity, the c2 / c4 / c5 '
+                         'sweep and the multi-rank exposed-wait figure')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's loss and the model state it left (seeded sample) as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-sweep', action='store_true', help='with --full: skip the c2 / c4 / c5 lines after the headline (N=1, c3 only)')
     ap.add_argument('--fwd-only', action='store_true', help='diagnostic (SURVEY 8d "also report fwd-only"): time the training-mode forward alone')
     ap.add_argument('--per-step', action='store_true', help='diagnostic: print per-step GPU times (HIP events, no extra syncs)')
     args = ap.parse_args()
@@ -401,11 +442,12 @@ def main():
     if world > 1:
         broadcast_module_state(model)
     trainer = Trainer(model, lr=3e-3, clip_value=0.8, global_batch=B * world)
-    trainer.sync.profile = world > 1                                          # HIP events around the all-reduce waits (dist.exposed_wait_ms_per_step)
+    trainer.sync.profile = world > 1 and args.full                            # HIP events around the all-reduce waits (dist.exposed_wait_ms_per_step)
     audio, lengths, targets, tl = synthetic_batch(B, T, cfg['model']['vocab_size'], seed=rank)
 
     timer = GemmTimer()
-    timer.install()
+    if args.full:
+        timer.install()
     run_step = trainer.step
     if args.fwd_only:
         def run_step(audio, lengths, targets, tl):
@@ -418,16 +460,17 @@ def main():
         torch.cuda.synchronize()
 
     loss = None
-    timer.count_only = True
+    timer.count_only = args.full
     for i in range(max(args.warmup, 1)):
         loss = run_step(audio, lengths, targets, tl)
         if i == 0:
             timer.count_only = False
-    timer.prepare(timer.calls * args.steps)
+    if args.full:
+        timer.prepare(timer.calls * args.steps)
     import gc
     gc.collect(); gc.disable()                                       # no collector pauses inside the timed region
     sync()
-    timer.enabled = True
+    timer.enabled = args.full
     t0 = time.perf_counter()
     step_ev = []
     for _ in range(args.steps):
@@ -449,10 +492,6 @@ def main():
 
     if rank == 0:
         frames = B * T * world * args.steps
-        att, hbm = timer.extra_summary()
-        roof = timer.summary()
-        if roof is not None:
-            roof['attention'], roof['hbm'] = att, hbm
         res = {
             'metric': 'spectrogram-frames/sec (6L/768D, seq=16384)' if args.config == 'c3' else f'spectrogram-frames/sec ({args.config}: {cfg["name"]})',
             'value': round(frames / dt, 1), 'unit': 'spectrogram-frames/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -461,8 +500,17 @@ def main():
             'config': {'workload': cfg['name'] + (', forward only (train mode, no_grad)' if args.fwd_only else ', fwd+CTC+bwd+clip+MADGRAD'), 'per_gpu_batch': B, 'global_batch': B * world, 'seq_len': T,
                        'parallelism': f'dp{world}', 'loss_last_step': round(float(loss), 3)},
             'per_gpu_value': round(frames / dt / world, 1),
-            'roofline': roof,
         }
+        if args.dump_outputs:
+            # what the caller of the timed path holds after its last step; inputs are seeded (model: 12345, batch: rank)
+            name = 'final_posteriors_0_0_0' if args.fwd_only else 'loss'
+            dump_outputs(args.dump_outputs, {name: loss.reshape(1)}, model)
+        if args.full:
+            att, hbm = timer.extra_summary()
+            roof = timer.summary()
+            if roof is not None:
+                roof['attention'], roof['hbm'] = att, hbm
+            res['roofline'] = roof
         if world > 1:
             # what an N-GPU deviation from linear is made of: the exchange is one all-reduce(SUM) per 64 MiB slice of the flat f32
             # gradient buffer, issued from the backward as soon as a slice is final; `exposed_wait_ms_per_step` is how long the
@@ -471,10 +519,11 @@ def main():
             res['dist'] = {'backend': backend + (' (RCCL over xGMI)' if backend == 'nccl' else ''), 'world_size': dist.get_world_size(),
                            'allreduce_bytes_per_step_per_rank': int(sy.flat_grad.numel() * 4), 'buckets': len(sy.buckets),
                            'exposed_wait_ms_per_step': sy.exposed_wait_ms(args.steps), 'single_device_rehearsal': bool(os.environ.get('SCONF_SINGLE_DEVICE'))}
-        if world == 1 and not args.no_cpu_baseline and args.config == 'c5':
+        cpu = args.full and world == 1 and not args.no_cpu_baseline
+        if cpu and args.config == 'c5':
             # the oracle writes attention out as an explicit (H, N, N) f32 matrix: 17 GB per layer at N = 16384, not a bounded sample
             res['cpu_baseline'] = None
-        elif world == 1 and not args.no_cpu_baseline:
+        elif cpu:
             del trainer, model, audio
             Fn_clear()
             res['cpu_baseline'] = cpu_baseline(args.config)
@@ -482,7 +531,7 @@ def main():
             res['gpu_over_cpu'] = round(res['value'] / res['cpu_baseline']['value'], 1)
             if args.config == 'c3':
                 res['cpu_baseline_t1024'] = cpu_baseline('c2', budget_s=4.0, parity=False)
-        if world == 1 and args.config == 'c3' and not args.no_sweep and not args.fwd_only:
+        if args.full and world == 1 and args.config == 'c3' and not args.no_sweep and not args.fwd_only:
             # the other north-star contexts (1024 and 131072 frames; the 9-layer model) through the same code path, after - and
             # outside - the timed region of the headline
             trainer = model = audio = None

@@ -125,8 +125,11 @@ int sconf_softmax_bwd(int mode, const void* y, int y_dtype, const void* dy, int 
  * the same pass; needs `workspace` of sconf_softmax_bwd_workspace(M, C) floats. */
 int64_t sconf_softmax_bwd_workspace(int64_t M, int64_t C);
 
-/* out[n] += alpha * sum_m x[m][n]  (bias gradients). */
-int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, sconf_stream_t stream);
+/* out[n] += alpha * sum_m x[m][n]  (bias gradients).  Summed in a fixed order (the same result every run): workspace of
+ * sconf_colsum_workspace(M, N) bytes (0: none needed). */
+int64_t sconf_colsum_workspace(int64_t M, int64_t N);
+int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
+                 int64_t workspace_bytes, sconf_stream_t stream);
 /* zero rows n >= lengths[b] of x[B][N][d] in place (attention.py:511,546-547; convolution.py:109-110). */
 int sconf_mask_rows(void* x, int dtype, const int32_t* lengths, int64_t B, int64_t N, int64_t d, sconf_stream_t stream);
 
@@ -148,35 +151,46 @@ int sconf_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
                    const float* rot_cos /*nullable: f32 (N, D/2); with rot_sin: dq, dk come back as gradients of the UNROTATED q, k*/,
                    const float* rot_sin, sconf_stream_t stream);
 
-/* Conformer conv module, token-major (convolution.py:103-124; conv1dFunc seam convolution.py:6-22; batchrenorm.py:52-92). */
+/* Conformer conv module, token-major (convolution.py:103-124; conv1dFunc seam convolution.py:6-22; batchrenorm.py:52-92).
+ * The statistics and parameter gradients are summed in a fixed order through the caller's workspace (sizes from the
+ * *_workspace queries, in bytes): the same result every run. */
+int64_t sconf_glu_dwconv_fwd_workspace(int64_t B, int64_t N, int64_t d);
 int sconf_glu_dwconv_fwd(const void* g, const int32_t* lengths, const float* w, const float* bias, void* h, double* stats,
-                         int64_t B, int64_t N, int64_t d, int64_t ksize, sconf_stream_t stream);
+                         void* workspace, int64_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t ksize,
+                         sconf_stream_t stream);
 int sconf_brn_finalize(const double* stats, int64_t count, float* running_mean, float* running_std,
                        int64_t* num_batches_tracked, const float* weight, const float* bias, float* coef, int64_t d,
                        int training, float eps, float momentum, sconf_stream_t stream);
 int sconf_affine_silu_fwd(const void* h, const float* coef, void* y, int64_t M, int64_t d, sconf_stream_t stream);
+int64_t sconf_convmod_bwd_workspace(int64_t B, int64_t N, int64_t d, int64_t ksize, int colsum);
 int sconf_convmod_bwd(const void* dy, const void* h, const void* g, const int32_t* lengths, const float* w,
                       const float* brn_weight, const float* coef, double* red, float* bcoef, void* dg, float* dw,
-                      float* dbias, float* dbrn_weight, float* dbrn_bias, float* dg_colsum, int64_t B, int64_t N, int64_t d,
-                      int64_t ksize, int training, float eps, sconf_stream_t stream);
+                      float* dbias, float* dbrn_weight, float* dbrn_bias, float* dg_colsum, void* workspace,
+                      int64_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t ksize, int training, float eps,
+                      sconf_stream_t stream);
 
 /* ConvSubsampling 'dw_striding' x8, channels-last (subsampling.py:276-321, 384-428). */
 int sconf_sub_conv0_fwd(const void* x, int x_dtype, const float* w, const float* bias, void* y, int64_t B, int64_t F,
                         int64_t T, int64_t C, sconf_stream_t stream);
 int sconf_sub_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int64_t B, int64_t Ti, int64_t Fi,
                          int64_t C, sconf_stream_t stream);
+/* parameter gradients summed in a fixed order through the workspace (sconf_sub_dwconv_bwd_workspace bytes) */
+int64_t sconf_sub_dwconv_bwd_workspace(int64_t B, int64_t Ti, int64_t Fi, int64_t C, int colsum);
 int sconf_sub_dwconv_bwd(const void* dout, const float* w, const void* pre_in, void* dpre_in, float* dw, float* dbias,
                          float* dpre_colsum /*nullable, f32 [C], accumulated: column sums of dpre_in = bias gradient of the 1x1 conv before it*/,
-                         int64_t B, int64_t Ti, int64_t Fi, int64_t C, sconf_stream_t stream);
+                         void* workspace, int64_t workspace_bytes, int64_t B, int64_t Ti, int64_t Fi, int64_t C, sconf_stream_t stream);
 int sconf_sub_conv0_bwd(const void* dpre0, const void* x, int x_dtype, float* dw, float* dbias, int64_t B, int64_t F,
                         int64_t T, int64_t C, sconf_stream_t stream);
 /* Fused stage 0->1 (conv0 + SiLU + first depthwise conv) without the (B,T/2,F/2,C) intermediate, and its parameter-gradient
  * backward (dw0,db0,dwd,dbd ACCUMULATED) from dd1 (B,T4,F4,C) bf16.  subsampling.py:299-318. */
 int sconf_sub_stage01_fwd(const void* x, int x_dtype, const float* w0, const float* b0, const float* wd, const float* bd,
                           void* d1, int64_t B, int64_t F, int64_t T, int64_t C, sconf_stream_t stream);
+/* the MFMA backward sums the gradients in a fixed order through the workspace (sconf_sub_stage01_bwd_workspace bytes; 0 when
+ * the shape goes to the VALU kernel, whose sums are atomic) */
+int64_t sconf_sub_stage01_bwd_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
 int sconf_sub_stage01_bwd(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
-                          float* dw0, float* db0, float* dwd, float* dbd, int64_t B, int64_t F, int64_t T, int64_t C,
-                          sconf_stream_t stream);
+                          float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                          int64_t B, int64_t F, int64_t T, int64_t C, sconf_stream_t stream);
 int sconf_sub_silu_transpose(int bwd, const void* pre, const void* ds, void* out, int64_t rows, int64_t F8, int64_t C,
                              sconf_stream_t stream);
 
@@ -218,7 +232,9 @@ int sconf_overlap_finalize(const float* acc, const float* count, float* out, int
 int sconf_argmax_rows(const float* x, int64_t M, int64_t C, int32_t* idx, sconf_stream_t stream);
 
 /* Fused MADGRAD + global-norm clip over flat f32 buffers (lcasr/optim/madgrad.py:81-212, exp/train.py:46-61). */
-int sconf_sumsq(const float* g, int64_t n, double* out, sconf_stream_t stream);
+/* *out += sum(g^2), per-workgroup sums added in a fixed order: workspace of sconf_sumsq_workspace(n) bytes */
+int64_t sconf_sumsq_workspace(int64_t n);
+int sconf_sumsq(const float* g, int64_t n, double* out, void* workspace, int64_t workspace_bytes, sconf_stream_t stream);
 /* k = steps applied so far: from the host, or read from k_dev (device int64) when k_dev != NULL.  At k == 0 the kernel creates
  * x0 := p (the reference creates its state lazily at the first step, madgrad.py:121-125).  A step whose gradient norm is not
  * finite is skipped; sconf_madgrad_advance (once per optimiser step, after the per-group launches) then leaves *k_dev alone,

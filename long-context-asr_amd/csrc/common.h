@@ -142,3 +142,44 @@ __device__ __forceinline__ float dgeluf_(float x) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---- fixed-order accumulation ----------------------------------------------------------------
+// Float atomics from many workgroups onto one address add up in arrival order, which changes from run to run, and so would
+// the training step.  Kernels that add ONE value per (workgroup, address) instead get a zeroed row of a slab each (they move
+// their output pointers by their row * stride), and det_finish adds the rows into the real outputs in row order.  The slab is
+// the caller's workspace (each entry point has a sconf_*_workspace size query), ordered on the caller's stream.
+template <typename T> struct DetSegs { T* out[4]; long off[4]; long n[4]; int k; };
+
+// slab (rows, stride): column j of segment i is added to out[i][j - off[i]].  Block = 64 columns x 16 waves; wave w sums rows
+// w, w + 16, ... and wave 0 adds the 16 partial sums in order.
+template <typename T>
+__global__ __launch_bounds__(1024) void det_reduce_kernel(const T* __restrict__ slab, long rows, long stride, DetSegs<T> s) {
+    __shared__ T red[16][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long col = (long)blockIdx.x * 64 + lane;
+    T a = 0;
+    if (col < stride) {
+#pragma unroll 8
+        for (long r = wv; r < rows; r += 16) a += slab[r * stride + col];
+    }
+    red[wv][lane] = a;
+    __syncthreads();
+    if (wv == 0 && col < stride) {
+        T t = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += red[k][lane];
+        for (int i = 0; i < s.k; ++i)
+            if (col >= s.off[i] && col < s.off[i] + s.n[i]) s.out[i][col - s.off[i]] += t;
+    }
+}
+
+// the workspace as a zeroed (rows, stride) slab of T, or nullptr when it is missing or too small
+template <typename T> T* det_begin(void* ws, int64_t ws_bytes, long rows, long stride, hipStream_t st) {
+    const size_t bytes = (size_t)rows * stride * sizeof(T);
+    if (!ws || ws_bytes < (int64_t)bytes) return nullptr;
+    if (hipMemsetAsync(ws, 0, bytes, st) != hipSuccess) return nullptr;
+    return (T*)ws;
+}
+template <typename T> void det_finish(const T* slab, long rows, long stride, const DetSegs<T>& s, hipStream_t st) {
+    hipLaunchKernelGGL(det_reduce_kernel<T>, dim3(cdiv(stride, 64)), dim3(1024), 0, st, slab, rows, stride, s);
+}

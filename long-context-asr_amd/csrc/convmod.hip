@@ -34,9 +34,10 @@ struct SlabGeo {
     }
 };
 // sum v[CV] (this thread's channels) over the workgroup's slabs; thread (sl==0) ends up owning nothing special: instead
-// lane i of the first cpb*CV threads adds channel (blockIdx.y*cpb*CV + i).  `sh` needs 1024 floats.
+// lane i of the first cpb*CV threads adds channel (blockIdx.y*cpb*CV + i).  `sh` needs 1024 floats.  det_stride: `out` is a
+// fixed-order slab (common.h), one row of det_stride elements per blockIdx.x (the only axis on which workgroups share channels).
 template <typename AT>
-__device__ __forceinline__ void slab_reduce_add(const float (&v)[CV], const SlabGeo& g, float* sh, AT* out, int d) {
+__device__ __forceinline__ void slab_reduce_add(const float (&v)[CV], const SlabGeo& g, float* sh, AT* out, int d, long det_stride) {
     __syncthreads();
     if (threadIdx.x < g.cpb * g.spb) {
 #pragma unroll
@@ -49,7 +50,7 @@ __device__ __forceinline__ void slab_reduce_add(const float (&v)[CV], const Slab
         if (c < d) {
             float a = 0.f;
             for (int s_ = 0; s_ < g.spb; ++s_) a += sh[s_ * nch + threadIdx.x];
-            atomicAdd(out + c, (AT)a);
+            atomicAdd(out + (long)blockIdx.x * det_stride + c, (AT)a);
         }
     }
 }
@@ -58,7 +59,7 @@ template <int K>
 __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const bf16* __restrict__ g, const int* __restrict__ len,
                                                              const float* __restrict__ w, const float* __restrict__ bias,
                                                              bf16* __restrict__ h, double* __restrict__ stats,
-                                                             int B, int N, int d, int TN) {
+                                                             int B, int N, int d, int TN, long det_stride) {
     constexpr int P = (K - 1) / 2;
     __shared__ float red[1024];
     const int CG = d / CV, spb = (N + TN - 1) / TN;
@@ -115,8 +116,8 @@ __global__ __launch_bounds__(256) void glu_dwconv_fwd_kernel(const bf16* __restr
         cva = nva; cga = nga;
     }
     if (stats) {
-        slab_reduce_add<double>(s1, geo, red, stats, d);
-        slab_reduce_add<double>(s2, geo, red, stats + d, d);
+        slab_reduce_add<double>(s1, geo, red, stats, d, det_stride);
+        slab_reduce_add<double>(s2, geo, red, stats + d, d, det_stride);
     }
 }
 
@@ -167,7 +168,7 @@ __global__ void affine_silu_fwd_kernel(const bf16* __restrict__ h, const float* 
 // pass 1 of the backward: per-channel sum(dz), sum(dz * xhat0), dz = dy * silu'(h*A+Bc), xhat0 = (h-mean)/s
 __global__ __launch_bounds__(256) void brn_bwd_reduce_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ h,
                                                              const float* __restrict__ coef, double* __restrict__ red,
-                                                             long M, int d, int rows_per_thread) {
+                                                             long M, int d, int rows_per_thread, long det_stride) {
     __shared__ float redb[1024];
     const int CG = d / CV;
     const SlabGeo geo(CG);
@@ -200,8 +201,8 @@ __global__ __launch_bounds__(256) void brn_bwd_reduce_kernel(const bf16* __restr
                 s1[e] += dz; s2[e] += dz * (x[u][e] - mean[e]) * is[e];
             }
     }
-    slab_reduce_add<double>(s1, geo, redb, red, d);
-    slab_reduce_add<double>(s2, geo, redb, red + d, d);
+    slab_reduce_add<double>(s1, geo, redb, red, d, det_stride);
+    slab_reduce_add<double>(s2, geo, redb, red + d, d, det_stride);
 }
 
 // bcoef rows: 0 k0, 1 k1, 2 k2  with  dh = k0*dz - k1 - xhat0*k2 ; accumulates d(weight), d(bias) of BatchRenorm
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(256) void dwconv_glu_bwd_kernel(const bf16* __restr
                                                              const float* __restrict__ w, const float* __restrict__ coef,
                                                              const float* __restrict__ bcoef, bf16* __restrict__ dg,
                                                              float* __restrict__ dwt, float* __restrict__ dbias,
-                                                             float* __restrict__ dgcs, int B, int N, int d, int TN) {
+                                                             float* __restrict__ dgcs, int B, int N, int d, int TN, long det_stride) {
     constexpr int P = (K - 1) / 2;
     __shared__ float redw[1024];
     const int CG = d / CV, spb = (N + TN - 1) / TN;
@@ -318,10 +319,10 @@ __global__ __launch_bounds__(256) void dwconv_glu_bwd_kernel(const bf16* __restr
         cur = nxt;
     }
     // gradients of the K taps are accumulated TRANSPOSED (dwt[j][c]) so a wave's atomics hit consecutive floats
-    slab_reduce_add<float>(gb, geo, redw, dbias, d);
+    slab_reduce_add<float>(gb, geo, redw, dbias, d, det_stride);
 #pragma unroll
-    for (int j = 0; j < K; ++j) slab_reduce_add<float>(gw[j], geo, redw, dwt + (long)j * d, d);
-    if (dgcs) { slab_reduce_add<float>(sv, geo, redw, dgcs, d); slab_reduce_add<float>(sg2, geo, redw, dgcs + d, d); }
+    for (int j = 0; j < K; ++j) slab_reduce_add<float>(gw[j], geo, redw, dwt + (long)j * d, d, det_stride);
+    if (dgcs) { slab_reduce_add<float>(sv, geo, redw, dgcs, d, det_stride); slab_reduce_add<float>(sg2, geo, redw, dgcs + d, d, det_stride); }
 }
 
 int pick_tn(long B, long N, long CG) {
@@ -335,17 +336,32 @@ int pick_tn(long B, long N, long CG) {
 // GLU(dim=channels) -> zero padded frames -> depthwise Conv1d(k, padding=(k-1)/2, groups=d, bias) and the batch
 // statistics BatchRenorm needs.  g: (B,N,2d) bf16 = pw1 output; h: (B,N,d) bf16; stats: f64 [2][d], PRE-ZEROED.
 // Replaces convolution.py:106-113 (+ flashfftconv conv1dFunc seam, convolution.py:6-22).
+static dim3 glu_fwd_grid(long B, long N, long d, int& TN) {
+    TN = pick_tn(B, N, d / CV);
+    const int cpb = (int)std::min<long>(64, d / CV), spbk = 256 / cpb;
+    return dim3(cdiv(B * cdiv(N, TN), spbk), cdiv(d / CV, cpb));
+}
+// bytes of workspace sconf_glu_dwconv_fwd needs when it takes the statistics: a fixed-order slab of 2d f64 per blockIdx.x
+SCONF_API int64_t sconf_glu_dwconv_fwd_workspace(int64_t B, int64_t N, int64_t d) {
+    if (B * N == 0 || d % CV != 0) return 0;
+    int TN; return (int64_t)glu_fwd_grid(B, N, d, TN).x * 2 * d * 8;
+}
 SCONF_API int sconf_glu_dwconv_fwd(const void* g, const int32_t* lengths, const float* w, const float* bias, void* h,
-                                   double* stats, int64_t B, int64_t N, int64_t d, int64_t ksize, hipStream_t stream) {
+                                   double* stats, void* workspace, int64_t workspace_bytes, int64_t B, int64_t N, int64_t d,
+                                   int64_t ksize, hipStream_t stream) {
     SCONF_REQUIRE(d % CV == 0, "sconf_glu_dwconv_fwd: d must be a multiple of 4");
     if (B * N == 0) return 0;
-    const int TN = pick_tn(B, N, d / CV);
-    const int cpb = (int)std::min<long>(64, d / CV), spbk = 256 / cpb;
-    dim3 grid(cdiv(B * cdiv(N, TN), spbk), cdiv(d / CV, cpb)), block(256);
-#define L(KK) hipLaunchKernelGGL((glu_dwconv_fwd_kernel<KK>), grid, block, 0, stream, (const bf16*)g, lengths, w, bias, (bf16*)h, stats, (int)B, (int)N, (int)d, TN)
-    switch (ksize) { case 3: L(3); break; case 5: L(5); break; case 7: L(7); break; case 9: L(9); break;
-        default: return sconf_set_error("sconf_glu_dwconv_fwd: unsupported kernel size %ld (3,5,7,9)", (long)ksize); }
+    int TN;
+    const dim3 grid = glu_fwd_grid(B, N, d, TN), block(256);
+    SCONF_REQUIRE(ksize == 3 || ksize == 5 || ksize == 7 || ksize == 9, "sconf_glu_dwconv_fwd: unsupported kernel size %ld (3,5,7,9)", (long)ksize);
+    // the statistics go to a fixed-order slab, one row per blockIdx.x, then into stats
+    double* sl = stats ? det_begin<double>(workspace, workspace_bytes, grid.x, 2 * d, stream) : nullptr;
+    SCONF_REQUIRE(!stats || sl, "sconf_glu_dwconv_fwd: needs %ld bytes of workspace (sconf_glu_dwconv_fwd_workspace)",
+                  (long)sconf_glu_dwconv_fwd_workspace(B, N, d));
+#define L(KK) hipLaunchKernelGGL((glu_dwconv_fwd_kernel<KK>), grid, block, 0, stream, (const bf16*)g, lengths, w, bias, (bf16*)h, sl, (int)B, (int)N, (int)d, TN, 2 * d)
+    switch (ksize) { case 3: L(3); break; case 5: L(5); break; case 7: L(7); break; default: L(9); break; }
 #undef L
+    if (stats) det_finish<double>(sl, grid.x, 2 * d, DetSegs<double>{{stats}, {0}, {2 * d}, 1}, stream);
     SCONF_LAUNCH_OK("sconf_glu_dwconv_fwd");
     return 0;
 }
@@ -376,27 +392,60 @@ SCONF_API int sconf_affine_silu_fwd(const void* h, const float* coef, void* y, i
 // red: f64 [2][d] scratch PRE-ZEROED; bcoef: f32 [3][d] scratch.  Writes dg (B,N,2d) bf16; ACCUMULATES (+=)
 // d(dw weight) TRANSPOSED as [k][d] (the caller transposes the tiny tensor back), d(dw bias) [d], d(brn weight) [d],
 // d(brn bias) [d]; dg_colsum (optional, [2d]) += column sums of dg = the pointwise_conv1 bias gradient (convolution.py:100).
+// geometry of sconf_convmod_bwd: rows of the statistics slab (rrows, 2d f64 each) and of the gradient slab (grid.x, gst f32 each)
+struct ConvmodBwdGeo { int rpt, cpb, spbk, rrows, TN; dim3 grid; long gst; };
+static ConvmodBwdGeo convmod_bwd_geo(long B, long N, long d, long ksize, bool colsum) {
+    ConvmodBwdGeo q;
+    const long M = B * N;
+    const int CG = (int)(d / CV);
+    q.rpt = 64;
+    while (q.rpt > 8 && cdiv(M, q.rpt) * CG < 131072) q.rpt >>= 1;
+    q.cpb = std::min(64, CG); q.spbk = 256 / q.cpb;
+    q.rrows = cdiv(cdiv(M, q.rpt), q.spbk);
+    q.TN = pick_tn(B, N, CG);
+    q.grid = dim3(cdiv(B * cdiv(N, q.TN), q.spbk), cdiv(CG, q.cpb));
+    q.gst = d + ksize * d + (colsum ? 2 * d : 0);           // slab row: [dbias d | dw K*d | dg_colsum 2d]
+    return q;
+}
+// bytes of workspace sconf_convmod_bwd needs (the two slabs use it one after the other)
+SCONF_API int64_t sconf_convmod_bwd_workspace(int64_t B, int64_t N, int64_t d, int64_t ksize, int colsum) {
+    if (B * N == 0 || d % CV != 0) return 0;
+    const ConvmodBwdGeo q = convmod_bwd_geo(B, N, d, ksize, colsum != 0);
+    return std::max<int64_t>((int64_t)q.rrows * 2 * d * 8, (int64_t)q.grid.x * q.gst * 4);
+}
 SCONF_API int sconf_convmod_bwd(const void* dy, const void* h, const void* g, const int32_t* lengths, const float* w,
                                 const float* brn_weight, const float* coef, double* red, float* bcoef, void* dg,
                                 float* dw, float* dbias, float* dbrn_weight, float* dbrn_bias, float* dg_colsum,
+                                void* workspace, int64_t workspace_bytes,
                                 int64_t B, int64_t N, int64_t d, int64_t ksize, int training, float eps, hipStream_t stream) {
     SCONF_REQUIRE(d % CV == 0, "sconf_convmod_bwd: d must be a multiple of 4");
     const long M = B * N;
     if (M == 0) return 0;
     const int CG = (int)(d / CV);
-    int rpt = 64;
-    while (rpt > 8 && cdiv(M, rpt) * CG < 131072) rpt >>= 1;
-    const int cpb = std::min(64, CG), spbk = 256 / cpb;
-    hipLaunchKernelGGL(brn_bwd_reduce_kernel, dim3(cdiv(cdiv(M, rpt), spbk), cdiv(CG, cpb)), dim3(256), 0, stream,
-                       (const bf16*)dy, (const bf16*)h, coef, red, M, (int)d, rpt);
+    SCONF_REQUIRE(ksize == 3 || ksize == 5 || ksize == 7 || ksize == 9, "sconf_convmod_bwd: unsupported kernel size %ld (3,5,7,9)", (long)ksize);
+    const ConvmodBwdGeo q = convmod_bwd_geo(B, N, d, ksize, dg_colsum != nullptr);
+    const int rpt = q.rpt, cpb = q.cpb, rrows = q.rrows;
+    SCONF_REQUIRE(workspace && workspace_bytes >= sconf_convmod_bwd_workspace(B, N, d, ksize, dg_colsum != nullptr),
+                  "sconf_convmod_bwd: needs %ld bytes of workspace (sconf_convmod_bwd_workspace)",
+                  (long)sconf_convmod_bwd_workspace(B, N, d, ksize, dg_colsum != nullptr));
+    // both reductions through fixed-order slabs (common.h), one row per blockIdx.x
+    double* rsl = det_begin<double>(workspace, workspace_bytes, rrows, 2 * d, stream);
+    SCONF_REQUIRE(rsl, "sconf_convmod_bwd: workspace memset failed");
+    hipLaunchKernelGGL(brn_bwd_reduce_kernel, dim3(rrows, cdiv(CG, cpb)), dim3(256), 0, stream,
+                       (const bf16*)dy, (const bf16*)h, coef, rsl, M, (int)d, rpt, 2 * d);
+    det_finish<double>(rsl, rrows, 2 * d, DetSegs<double>{{red}, {0}, {2 * d}, 1}, stream);
     hipLaunchKernelGGL(brn_bwd_finalize_kernel, dim3(cdiv(d, 256)), dim3(256), 0, stream, red, (double)M, coef, brn_weight,
                        bcoef, dbrn_weight, dbrn_bias, (int)d, training, eps);
-    const int TN = pick_tn(B, N, CG);
-    dim3 grid(cdiv(B * cdiv(N, TN), spbk), cdiv(CG, cpb)), block(256);
-#define L(KK) hipLaunchKernelGGL((dwconv_glu_bwd_kernel<KK>), grid, block, 0, stream, (const bf16*)dy, (const bf16*)h, (const bf16*)g, lengths, w, coef, bcoef, (bf16*)dg, dw, dbias, dg_colsum, (int)B, (int)N, (int)d, TN)
-    switch (ksize) { case 3: L(3); break; case 5: L(5); break; case 7: L(7); break; case 9: L(9); break;
-        default: return sconf_set_error("sconf_convmod_bwd: unsupported kernel size %ld (3,5,7,9)", (long)ksize); }
+    const int TN = q.TN;
+    const dim3 grid = q.grid, block(256);
+    const long gst = q.gst;
+    // the same workspace again (the reduce kernel above is done with it: same stream)
+    float* gsl = det_begin<float>(workspace, workspace_bytes, grid.x, gst, stream);
+    SCONF_REQUIRE(gsl, "sconf_convmod_bwd: workspace memset failed");
+#define L(KK) hipLaunchKernelGGL((dwconv_glu_bwd_kernel<KK>), grid, block, 0, stream, (const bf16*)dy, (const bf16*)h, (const bf16*)g, lengths, w, coef, bcoef, (bf16*)dg, gsl + d, gsl, dg_colsum ? gsl + d + ksize * d : nullptr, (int)B, (int)N, (int)d, TN, gst)
+    switch (ksize) { case 3: L(3); break; case 5: L(5); break; case 7: L(7); break; default: L(9); break; }
 #undef L
+    det_finish<float>(gsl, grid.x, gst, DetSegs<float>{{dbias, dw, dg_colsum}, {0, d, d + ksize * d}, {d, ksize * d, dg_colsum ? 2 * d : 0}, dg_colsum ? 3 : 2}, stream);
     SCONF_LAUNCH_OK("sconf_convmod_bwd");
     return 0;
 }

@@ -450,7 +450,10 @@ __global__ __launch_bounds__(256) void ctc_grad_logits_kernel(const float* __res
                                                               bf16* __restrict__ dlogits, float* __restrict__ slab,
                                                               long rows, int B, int N, int C, int Smax, int Lmax, int blank, int rows_per_block) {
     extern __shared__ float occ[];                      // [C]
-    __shared__ float ssum;
+    __shared__ float wpart[2][4];                       // per wave: sum of all occupancies, sum of the blank ones
+    constexpr int LCH = 1024;                           // label states staged per chunk
+    __shared__ int stg_lab[LCH];
+    __shared__ float stg_occ[LCH];
     constexpr int MAXIT = 8;                            // C <= 8192
     float cs[MAXIT][4];
 #pragma unroll
@@ -486,26 +489,44 @@ __global__ __launch_bounds__(256) void ctc_grad_logits_kernel(const float* __res
             const int c = k * 1024 + threadIdx.x * 4;
             if (c < C) lv[k] = *reinterpret_cast<const float4*>(lr + c);
         }
-        __syncthreads();                                // the previous row's reads of occ / ssum are done
+        __syncthreads();                                // the previous row's reads of occ / wpart are done
         for (int c = threadIdx.x; c < C; c += 256) occ[c] = 0.f;
-        if (threadIdx.x == 0) ssum = 0.f;
         __syncthreads();
-        const int L = 2 * tg_len[b] + 1;
+        const int S_ = tg_len[b];
         const long base = bt * Lmax;
-        // Half of the states are the blank: as LDS atomics they would all hit ONE address (a 32-way conflict per wave
-        // instruction).  The stride (256) is even, so a thread sees either blanks only or labels only: blanks are summed in
-        // registers, then per wave (no barrier), and added with one atomic per wave - as is S, the sum of all occupancies.
+        // Every sum here is taken in a fixed order, so the gradient is the same from run to run (LDS atomics from different
+        // waves onto one address would add up in arrival order).  Blank states (half of them, one address) are summed in
+        // registers, then per wave.  Label states: all threads compute the occupancies of a chunk and stage them in LDS with
+        // their labels; then wave w adds those whose label is w mod 4, so every state of one label is added by one wave, in
+        // state order.  The per-wave sums (blank, S = all occupancies) are added in wave order.
+        const int wvi = threadIdx.x >> 6, ln = threadIdx.x & 63;
         float tot = 0.f, blk = 0.f;
         const float adj = (float)(offs[bt] + offs[(long)B * N + bt] + offs[2L * B * N + b]);      // see ctc_grad_kernel
-        for (int s = threadIdx.x; s < L; s += 256) {
-            const float o = __expf(alpha[base + s] + beta[base + s] - lpg[base + s] + adj);
-            if (s & 1) atomicAdd(&occ[targets[(long)b * Smax + (s >> 1)]], o); else blk += o;
-            tot += o;
+        for (int k = threadIdx.x; k <= S_; k += 256) {                   // blank states s = 2k
+            const long s = base + 2 * k;
+            const float o = __expf(alpha[s] + beta[s] - lpg[s] + adj);
+            blk += o; tot += o;
+        }
+        for (int k0 = 0; k0 < S_; k0 += LCH) {                           // label states s = 2k + 1, LCH at a time
+            const int n = min(LCH, S_ - k0);
+            for (int j = threadIdx.x; j < n; j += 256) {
+                const long s = base + 2 * (k0 + j) + 1;
+                const float o = __expf(alpha[s] + beta[s] - lpg[s] + adj);
+                stg_lab[j] = targets[(long)b * Smax + k0 + j]; stg_occ[j] = o;
+                tot += o;
+            }
+            __syncthreads();
+            for (int j = ln; j < n; j += 64) {
+                const int lab = stg_lab[j];
+                if ((lab & 3) == wvi) atomicAdd(&occ[lab], stg_occ[j]);
+            }
+            if (k0 + LCH < S_) __syncthreads();                          // (uniform) the next chunk overwrites the staging
         }
         tot = wave_sum(tot); blk = wave_sum(blk);
-        if ((threadIdx.x & 63) == 0) { atomicAdd(&ssum, tot); atomicAdd(&occ[blank], blk); }
-        __syncthreads();                                // occ and ssum are complete
-        const float S = ssum;
+        if (ln == 0) { wpart[0][wvi] = tot; wpart[1][wvi] = blk; }
+        __syncthreads();                                // occ and the per-wave sums are complete
+        const float S = ((wpart[0][0] + wpart[0][1]) + wpart[0][2]) + wpart[0][3];
+        const float oblank = ((wpart[1][0] + wpart[1][1]) + wpart[1][2]) + wpart[1][3];     // added to occ[blank] on use
         const float g = grad_out ? grad_out[b] : 1.f, ls = lse[bt];
 #pragma unroll
         for (int k = 0; k < MAXIT; ++k) {
@@ -513,7 +534,10 @@ __global__ __launch_bounds__(256) void ctc_grad_logits_kernel(const float* __res
             if (c < C) {
                 float v[4] = {lv[k].x, lv[k].y, lv[k].z, lv[k].w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] = g * (__expf(v[e] - ls) * S - occ[c + e]); cs[k][e] += (float)(bf16)v[e]; }
+                for (int e = 0; e < 4; ++e) {
+                    const float oc = c + e == blank ? occ[c + e] + oblank : occ[c + e];
+                    v[e] = g * (__expf(v[e] - ls) * S - oc); cs[k][e] += (float)(bf16)v[e];
+                }
                 store4(out + c, v);
             }
         }
@@ -529,7 +553,9 @@ __global__ __launch_bounds__(256) void ctc_grad_logits_kernel(const float* __res
 
 }  // namespace
 
-SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, hipStream_t stream);
+SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream);
+SCONF_API int64_t sconf_colsum_workspace(int64_t M, int64_t N);
 
 // Workspace contract: lpg, alpha, beta are f32 [B][N][Lmax] with Lmax = 2*Smax+1 (caller-allocated); offs is f64 [2*B*N + B]:
 // the per-frame offsets of the renormalised alpha rows, of the beta rows, and the nll in f64 (read back by the backward).
@@ -606,7 +632,11 @@ static int ctc_bwd_slabs() {                            // workgroups of the fus
     return v;
 }
 #define CTC_BWD_SLABS ctc_bwd_slabs()
-SCONF_API int64_t sconf_ctc_bwd_logits_workspace(int64_t rows, int64_t C) { return (int64_t)std::min<long>(rows, CTC_BWD_SLABS) * C; }
+// floats: the per-workgroup column-sum slabs, then the workspace of the column sum over them
+SCONF_API int64_t sconf_ctc_bwd_logits_workspace(int64_t rows, int64_t C) {
+    const long slabs = std::min<long>(rows, CTC_BWD_SLABS);
+    return (int64_t)(slabs * C + (sconf_colsum_workspace(slabs, C) + 3) / 4);
+}
 // dlogits (B,N,C) bf16 = d nll / d logits (CTC gradient through log_softmax), scaled by grad_out[b] (null = 1).
 // colsum_out (optional, f32 [C], ACCUMULATED): column sums of dlogits - the decoder bias gradient; needs the workspace
 // (sconf_ctc_bwd_logits_workspace(B * N, C) floats).
@@ -625,7 +655,8 @@ SCONF_API int sconf_ctc_bwd_logits(const float* logits, const float* lse, const 
                        input_lengths, target_lengths, grad_out, (bf16*)dlogits_bf16, colsum_out ? workspace : nullptr, rows, (int)B, (int)N, (int)C,
                        (int)Smax, Lmax, blank, rpb);
     SCONF_LAUNCH_OK("sconf_ctc_bwd_logits");
-    if (colsum_out) return sconf_colsum(workspace, SCONF_F32, colsum_out, (int64_t)grid, C, C, 1.f, stream);     // += over the slabs
+    if (colsum_out) return sconf_colsum(workspace, SCONF_F32, colsum_out, (int64_t)grid, C, C, 1.f, workspace + (long)grid * C,   // += over the slabs
+                                        sconf_colsum_workspace(grid, C), stream);
     return 0;
 }
 

@@ -273,7 +273,9 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const TY* __restrict__
 
 // ---------------------------------------------------------------------------------------------
 // out[n] += alpha * sum_m x[m][n]   (bias gradients).  Block = 256 threads = 64 column-quads x 4 row lanes.
-template <typename T>
+// PART: the row block's sums go to out[blockIdx.y][N] (plain stores, alpha not applied) for a second, single-row-block pass that
+// adds them in a fixed order - float atomics from several row blocks would make the sum depend on their arrival order.
+template <typename T, bool PART = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, float* __restrict__ out, long M, int N, long ld,
                                                      int rows_per_block, float alpha) {
     __shared__ float sh[4][256];
@@ -293,7 +295,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, fl
     for (int e = 0; e < 4; ++e) sh[rl][cq * 4 + e] = a[e];
     __syncthreads();
     const int cc = blockIdx.x * 256 + threadIdx.x;
-    if (cc < N) atomicAdd(out + cc, alpha * (sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]));
+    if (cc >= N) return;
+    const float v = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (PART) out[(long)blockIdx.y * N + cc] = v;
+    else out[cc] += alpha * v;                                  // launched with gridDim.y == 1: the only writer of out[cc]
 }
 
 // Zero rows n >= len[b] of x[B][N][d] in place (attention.py:511,546-547; convolution.py:109-110).
@@ -420,9 +425,14 @@ SCONF_API int sconf_rowdot(const void* a, const void* b, const float* bias, floa
     return 0;
 }
 
-SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, hipStream_t stream);
-// floats of scratch sconf_softmax_bwd needs when it also produces the column sums of dx
-SCONF_API int64_t sconf_softmax_bwd_workspace(int64_t M, int64_t C) { return (int64_t)std::min<long>(M, SOFTMAX_BWD_SLABS) * C; }
+SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream);
+SCONF_API int64_t sconf_colsum_workspace(int64_t M, int64_t N);
+// floats of scratch sconf_softmax_bwd needs when it also produces the column sums of dx: the slabs, then the column sum's workspace
+SCONF_API int64_t sconf_softmax_bwd_workspace(int64_t M, int64_t C) {
+    const long slabs = std::min<long>(M, SOFTMAX_BWD_SLABS);
+    return (int64_t)(slabs * C + (sconf_colsum_workspace(slabs, C) + 3) / 4);
+}
 
 // colsum_out (optional, f32 [C], ACCUMULATED): column sums of dx, i.e. the bias gradient of the Linear that produced the logits.
 SCONF_API int sconf_softmax_bwd(int mode, const void* y, int y_dtype, const void* dy, int dy_dtype, void* dx, int dx_dtype,
@@ -444,21 +454,46 @@ SCONF_API int sconf_softmax_bwd(int mode, const void* y, int y_dtype, const void
 #undef D3
 #undef L
     SCONF_LAUNCH_OK("sconf_softmax_bwd");
-    if (colsum_out) return sconf_colsum(slab, SCONF_F32, colsum_out, (int64_t)g.x, C, C, 1.f, stream);     // += over the slabs
+    if (colsum_out) return sconf_colsum(slab, SCONF_F32, colsum_out, (int64_t)g.x, C, C, 1.f, slab + (long)g.x * C,     // += over the slabs
+                                        sconf_colsum_workspace(g.x, C), stream);
     return 0;
 }
 
-// out[n] += sum over rows (bias gradients of Linear / Conv layers).
-SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, hipStream_t stream) {
+// column blocks, row blocks, rows per row block of sconf_colsum
+static void colsum_geo(long M, long N, int& cb, int& rb, int& rpb) {
+    cb = cdiv(N, 256);
+    rb = std::max(1, std::min(cdiv(M, 64), 2048 / cb));
+    rpb = cdiv(M, rb);
+    rb = cdiv(M, rpb);
+}
+// bytes of workspace sconf_colsum needs (0: one row block, none)
+SCONF_API int64_t sconf_colsum_workspace(int64_t M, int64_t N) {
+    if (M <= 0 || N <= 0) return 0;
+    int cb, rb, rpb; colsum_geo(M, N, cb, rb, rpb);
+    return rb > 1 ? (int64_t)rb * N * 4 : 0;
+}
+
+// out[n] += sum over rows (bias gradients of Linear / Conv layers), in a fixed order: several row blocks write their sums to the
+// workspace (sconf_colsum_workspace(M, N) bytes) and one row block adds them up.
+SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream) {
     SCONF_REQUIRE(N % 4 == 0 && ld % 4 == 0, "sconf_colsum: N and ld must be multiples of 4");
     if (M == 0 || N == 0) return 0;
-    const int cb = cdiv(N, 256);
-    int rb = std::max(1, std::min(cdiv(M, 64), 2048 / cb));
-    const int rpb = cdiv(M, rb);
-    rb = cdiv(M, rpb);
+    int cb, rb, rpb; colsum_geo(M, N, cb, rb, rpb);
     dim3 g(cb, rb), b(256);
-    if (x_dtype == SCONF_BF16) hipLaunchKernelGGL((colsum_kernel<bf16>), g, b, 0, stream, (const bf16*)x, out, (long)M, (int)N, (long)ld, rpb, alpha);
-    else hipLaunchKernelGGL((colsum_kernel<float>), g, b, 0, stream, (const float*)x, out, (long)M, (int)N, (long)ld, rpb, alpha);
+    if (rb == 1) {
+        if (x_dtype == SCONF_BF16) hipLaunchKernelGGL((colsum_kernel<bf16>), g, b, 0, stream, (const bf16*)x, out, (long)M, (int)N, (long)ld, rpb, alpha);
+        else hipLaunchKernelGGL((colsum_kernel<float>), g, b, 0, stream, (const float*)x, out, (long)M, (int)N, (long)ld, rpb, alpha);
+        SCONF_LAUNCH_OK("sconf_colsum");
+        return 0;
+    }
+    // several row blocks: their sums to a slab (rb, N), then one row block adds the slab up in a fixed order (same result every run)
+    SCONF_REQUIRE(workspace && workspace_bytes >= sconf_colsum_workspace(M, N), "sconf_colsum: needs %ld bytes of workspace (sconf_colsum_workspace)",
+                  (long)sconf_colsum_workspace(M, N));
+    float* part = (float*)workspace;
+    if (x_dtype == SCONF_BF16) hipLaunchKernelGGL((colsum_kernel<bf16, true>), g, b, 0, stream, (const bf16*)x, part, (long)M, (int)N, (long)ld, rpb, 1.f);
+    else hipLaunchKernelGGL((colsum_kernel<float, true>), g, b, 0, stream, (const float*)x, part, (long)M, (int)N, (long)ld, rpb, 1.f);
+    hipLaunchKernelGGL((colsum_kernel<float>), dim3(cb, 1), b, 0, stream, (const float*)part, out, (long)rb, (int)N, (long)N, rb, alpha);
     SCONF_LAUNCH_OK("sconf_colsum");
     return 0;
 }

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     for (; i + 4 <= n; i += stride) { float v[4]; load4(g + i, v); acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
     if (i < n) for (long j = i; j < n && j < i + 4; ++j) acc += g[j] * g[j];
     acc = block_sum(acc, sh);
-    if (threadIdx.x == 0) atomicAdd(out, (double)acc);
+    if (threadIdx.x == 0) out[blockIdx.x] = (double)acc;     // one slot per workgroup: added up in a fixed order afterwards
 }
 
 // p_{k+1}: gss += lamb g^2 ; rms = cbrt(gss)+eps ; s += lamb g ; z = x0 - s/rms ; p = (1-ck) p + ck z,  lamb = lr sqrt(k+1)
@@ -84,11 +84,17 @@ __global__ void madgrad_advance_kernel(long* __restrict__ k_dev, const double* _
 
 }  // namespace
 
-// out (f64 scalar, PRE-ZEROED) += sum(g^2)
-SCONF_API int sconf_sumsq(const float* g, int64_t n, double* out, hipStream_t stream) {
+static int sumsq_blocks(long n) { return (int)std::min<long>(cdiv(n, 1024), 2048); }
+// bytes of workspace sconf_sumsq needs: one f64 per workgroup
+SCONF_API int64_t sconf_sumsq_workspace(int64_t n) { return n > 0 ? (int64_t)sumsq_blocks(n) * 8 : 0; }
+// out (f64 scalar, PRE-ZEROED) += sum(g^2), the per-workgroup sums added in workgroup order
+SCONF_API int sconf_sumsq(const float* g, int64_t n, double* out, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
     if (n == 0) return 0;
-    const int blocks = (int)std::min<long>(cdiv(n, 1024), 2048);
-    hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, stream, g, (long)n, out);
+    const int blocks = sumsq_blocks(n);
+    double* sl = det_begin<double>(workspace, workspace_bytes, blocks, 1, stream);
+    SCONF_REQUIRE(sl, "sconf_sumsq: needs %ld bytes of workspace (sconf_sumsq_workspace)", (long)sconf_sumsq_workspace(n));
+    hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, stream, g, (long)n, sl);
+    det_finish<double>(sl, blocks, 1, DetSegs<double>{{out}, {0}, {1}, 1}, stream);
     SCONF_LAUNCH_OK("sconf_sumsq");
     return 0;
 }

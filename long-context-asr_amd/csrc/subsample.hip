@@ -123,8 +123,12 @@ template <int CW>
 __global__ __launch_bounds__(512) void dwconv2d_bwd_kernel(const bf16* __restrict__ dout, const float* __restrict__ w,
                                                            const bf16* __restrict__ pre_in, bf16* __restrict__ dpre_in,
                                                            float* __restrict__ dw, float* __restrict__ dbias, float* __restrict__ dcolsum,
-                                                           int Ti, int Fi, int C, int To, int Fo, int PL, int iters) {
+                                                           int Ti, int Fi, int C, int To, int Fo, int PL, int iters, long det_stride) {
     __shared__ float red[512];
+    {   // the parameter gradients go to this workgroup's row of a fixed-order slab (common.h)
+        const long drow = ((long)blockIdx.y * gridDim.x + blockIdx.x) * det_stride;
+        dw += drow; dbias += drow; if (dcolsum) dcolsum += drow;
+    }
     const int cgs = C / CW;
     struct { int cg, plane, c0; bool active; } g;
     g.cg = threadIdx.x % cgs; g.plane = threadIdx.x / cgs; g.c0 = g.cg * CW; g.active = g.plane < PL;
@@ -542,7 +546,9 @@ int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const fl
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
 int sconf_dwconv_window_fwd(const void* x, const float* w, const float* bias, void* y, int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream);
 int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
-                           float* dw0, float* db0, float* dwd, float* dbd, int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
+                           float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
+int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
 namespace {
 
 struct LaunchGeo { int PL, iters, threads; dim3 grid; };
@@ -593,23 +599,45 @@ SCONF_API int sconf_sub_dwconv_fwd(const void* x, const float* w, const float* b
 // dpre_in = SiLU'(pre_in) * dwconv^T(dout);  dw/dbias ACCUMULATED (+=).  dpre_colsum (nullable, f32 [C], ACCUMULATED): the column sums of
 // dpre_in as stored (bf16) = the bias gradient of the 1x1 conv that produced pre_in, from the same pass (a separate column-sum
 // kernel re-read the 5.4 GB tensor: 0.95 ms per step at B = 128).
-SCONF_API int sconf_sub_dwconv_bwd(const void* dout, const float* w, const void* pre_in, void* dpre_in, float* dw, float* dbias,
-                                   float* dpre_colsum, int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream) {
-    SUB_REQ("sconf_sub_dwconv_bwd");
-    const int To = (int)((Ti - 1) / 2 + 1), Fo = (int)((Fi - 1) / 2 + 1);
-    if (B * Ti * Fi == 0) return 0;
+struct DwBwdGeo { int cw, PL, threads, iters; dim3 grid; };
+static DwBwdGeo dwconv_bwd_geo(long B, long Ti, long Fi, long C) {
+    DwBwdGeo q;
     long target = 512; int cw = 8;                             // few workgroups (each ends with 10 x C atomics), 16-B accesses
     if (const char* e = getenv("SCONF_SUB_DWBWD_CFG")) { int a = 0; long t = 0; if (sscanf(e, "%d,%ld", &a, &t) == 2) { cw = a; target = t; } }   // tuning
     const int cgs = (int)(C / cw);
-    SCONF_REQUIRE(cgs <= 256, "sconf_sub_dwconv_bwd: C too large");
     int nthr = 256;                                            // measured with all tap loads in flight: 3.3 -> 1.9 ms at B = 64
     if (const char* e = getenv("SCONF_SUB_DWBWD_THREADS")) { const int v = atoi(e); if (v == 256 || v == 512) nthr = v; }     // tuning
-    const int PL = std::max(1, nthr / cgs), threads = (cgs * PL + 63) / 64 * 64;
+    q.cw = cw;
+    q.PL = std::max(1, nthr / cgs); q.threads = (cgs * q.PL + 63) / 64 * 64;
     const long npos = (long)Ti * Fi, per_b = std::max<long>(1, target / B);
-    const int iters = (int)std::max<long>(1, cdiv(npos, (long)PL * per_b));
-    dim3 grid(cdiv(npos, (long)PL * iters), (unsigned)B);
-    if (cw == 8) hipLaunchKernelGGL((dwconv2d_bwd_kernel<8>), grid, dim3(threads), 0, stream, (const bf16*)dout, w, (const bf16*)pre_in, (bf16*)dpre_in, dw, dbias, dpre_colsum, (int)Ti, (int)Fi, (int)C, To, Fo, PL, iters);
-    else         hipLaunchKernelGGL((dwconv2d_bwd_kernel<4>), grid, dim3(threads), 0, stream, (const bf16*)dout, w, (const bf16*)pre_in, (bf16*)dpre_in, dw, dbias, dpre_colsum, (int)Ti, (int)Fi, (int)C, To, Fo, PL, iters);
+    q.iters = (int)std::max<long>(1, cdiv(npos, (long)q.PL * per_b));
+    q.grid = dim3(cdiv(npos, (long)q.PL * q.iters), (unsigned)B);
+    return q;
+}
+// bytes of workspace sconf_sub_dwconv_bwd needs: a fixed-order slab row [dw 9C | dbias C | dpre_colsum C] f32 per workgroup
+SCONF_API int64_t sconf_sub_dwconv_bwd_workspace(int64_t B, int64_t Ti, int64_t Fi, int64_t C, int colsum) {
+    if (B * Ti * Fi == 0 || C <= 0) return 0;
+    const DwBwdGeo q = dwconv_bwd_geo(B, Ti, Fi, C);
+    return (int64_t)q.grid.x * q.grid.y * (10 * C + (colsum ? C : 0)) * 4;
+}
+SCONF_API int sconf_sub_dwconv_bwd(const void* dout, const float* w, const void* pre_in, void* dpre_in, float* dw, float* dbias,
+                                   float* dpre_colsum, void* workspace, int64_t workspace_bytes, int64_t B, int64_t Ti, int64_t Fi,
+                                   int64_t C, hipStream_t stream) {
+    SUB_REQ("sconf_sub_dwconv_bwd");
+    const int To = (int)((Ti - 1) / 2 + 1), Fo = (int)((Fi - 1) / 2 + 1);
+    if (B * Ti * Fi == 0) return 0;
+    const DwBwdGeo q = dwconv_bwd_geo(B, Ti, Fi, C);
+    SCONF_REQUIRE(C / q.cw <= 256, "sconf_sub_dwconv_bwd: C too large");
+    const int cw = q.cw, PL = q.PL, threads = q.threads, iters = q.iters;
+    const dim3 grid = q.grid;
+    // slab row: [dw 9C | dbias C | dpre_colsum C], added into the gradients in workgroup order after the kernel
+    const long rows = (long)grid.x * grid.y, dst = 10 * C + (dpre_colsum ? C : 0);
+    float* sl = det_begin<float>(workspace, workspace_bytes, rows, dst, stream);
+    SCONF_REQUIRE(sl, "sconf_sub_dwconv_bwd: needs %ld bytes of workspace (sconf_sub_dwconv_bwd_workspace)", rows * dst * 4);
+    float* scs = dpre_colsum ? sl + 10 * C : nullptr;
+    if (cw == 8) hipLaunchKernelGGL((dwconv2d_bwd_kernel<8>), grid, dim3(threads), 0, stream, (const bf16*)dout, w, (const bf16*)pre_in, (bf16*)dpre_in, sl, sl + 9 * C, scs, (int)Ti, (int)Fi, (int)C, To, Fo, PL, iters, dst);
+    else         hipLaunchKernelGGL((dwconv2d_bwd_kernel<4>), grid, dim3(threads), 0, stream, (const bf16*)dout, w, (const bf16*)pre_in, (bf16*)dpre_in, sl, sl + 9 * C, scs, (int)Ti, (int)Fi, (int)C, To, Fo, PL, iters, dst);
+    det_finish<float>(sl, rows, dst, DetSegs<float>{{dw, dbias, dpre_colsum}, {0, 9 * C, 10 * C}, {9 * C, C, dpre_colsum ? C : 0}, dpre_colsum ? 3 : 2}, stream);
     SCONF_LAUNCH_OK("sconf_sub_dwconv_bwd");
     return 0;
 }
@@ -671,14 +699,18 @@ SCONF_API int sconf_sub_stage01_fwd(const void* x, int x_dtype, const float* w0,
 
 // Backward of the fused stage: parameter gradients of conv0 and of the first depthwise conv from dd1 (B,T4,F4,C) bf16;
 // all four outputs ACCUMULATED (+=).  (The mel input needs no gradient.)
+// bytes of workspace sconf_sub_stage01_bwd needs (the MFMA kernel's fixed-order gradient slab; 0 when it does not take the shape)
+SCONF_API int64_t sconf_sub_stage01_bwd_workspace(int64_t B, int64_t F, int64_t T, int64_t C) { return stage01_bwd_mfma_workspace(B, F, T, C); }
 SCONF_API int sconf_sub_stage01_bwd(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
-                                    float* dw0, float* db0, float* dwd, float* dbd, int64_t B, int64_t F, int64_t T, int64_t C,
-                                    hipStream_t stream) {
+                                    float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                                    int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     SCONF_REQUIRE(C % 4 == 0 && C / 4 <= 256, "sconf_sub_stage01_bwd: C must be a multiple of 4 and <= 1024");
     SCONF_REQUIRE(B <= 65535 && F <= 1024, "sconf_sub_stage01_bwd: B <= 65535 and F <= 1024");
     const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
     if (B * T4 * F4 == 0) return 0;
-    if (sconf_stage01_bwd_mfma(dd1, x, x_dtype, w0, b0, wd, dw0, db0, dwd, dbd, B, F, T, C, stream)) { SCONF_LAUNCH_OK("sconf_sub_stage01_bwd"); return 0; }
+    const int mf = sconf_stage01_bwd_mfma(dd1, x, x_dtype, w0, b0, wd, dw0, db0, dwd, dbd, workspace, workspace_bytes, B, F, T, C, stream);
+    if (mf < 0) return 1;                                      // (error already set)
+    if (mf) { SCONF_LAUNCH_OK("sconf_sub_stage01_bwd"); return 0; }
     int rw = 4; long target = 512;                             // measured best of {1,2,4} x {256..2048} at config 3
     if (const char* e = getenv("SCONF_SUB_BWD_CFG")) { int a = 0; long t = 0; if (sscanf(e, "%d,%ld", &a, &t) == 2) { rw = a; target = t; } }   // tuning
     auto lds_bytes = [&](int r) { return (size_t)((2 * r + 1) * F + 256) * 4 + (size_t)(r / 2 + 2) * F4 * C * 2; };

@@ -290,8 +290,13 @@ template <typename TX, int NCB>
 __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kernel(const TX* __restrict__ x, const float* __restrict__ w0g, const float* __restrict__ b0g,
                                                                   const float* __restrict__ wdg, const bf16* __restrict__ dd1,
                                                                   float* __restrict__ dw0, float* __restrict__ db0, float* __restrict__ dwd, float* __restrict__ dbd,
-                                                                  int F, int T, int C, int T2, int F2, int T4, int F4, int rows_per_block) {
+                                                                  int F, int T, int C, int T2, int F2, int T4, int F4, int rows_per_block,
+                                                                  long det_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    {   // the parameter gradients go to this workgroup's row of a fixed-order slab (common.h)
+        const long drow = ((long)blockIdx.y * gridDim.x + blockIdx.x) * det_stride;
+        dw0 += drow; db0 += drow; dwd += drow; dbd += drow;
+    }
     const int GS = 2 * C, GSLOT = (F4 + 2) * GS;          // a dd1 row + two zero bins (fo = F4, F4 + 1: taps past the last output)
     char* patch = smem;                                  // [2][PATCH_BYTES]
     char* gimg = smem + 2 * PATCH_BYTES;                 // [3][F4 + 2][C] bf16: slots to & 1, slot 2 = zeros (rows outside [0, T4))
@@ -464,26 +469,48 @@ int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const fl
     return 1;
 }
 
-int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
-                           float* dw0, float* db0, float* dwd, float* dbd, int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
-    if (C % 32 != 0 || C > 512 || F2 > PPOS) return 0;
-    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return 0;                   // A/B switch
-    if ((F4 * C) % 8 != 0) return 0;
+// whether the MFMA backward takes this shape, and its launch geometry
+static bool stage01_bwd_mfma_geo(long B, long F, long T, long C, dim3& grid, size_t& sh, int& rpb) {
+    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), F4 = (F2 - 1) / 2 + 1;
+    if (C % 32 != 0 || C > 512 || F2 > PPOS) return false;
+    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return false;               // A/B switch
+    if ((F4 * C) % 8 != 0) return false;
     const size_t gslot = (size_t)(F4 + 2) * 2 * C;
-    const size_t sh = 2 * (size_t)PATCH_BYTES + 3 * gslot;
-    if (sh > 80 * 1024) return 0;                                                               // two workgroups per CU
+    sh = 2 * (size_t)PATCH_BYTES + 3 * gslot;
+    if (sh > 80 * 1024) return false;                                                           // two workgroups per CU
     long target = 2048;
     if (const char* e = getenv("SCONF_SUB_BWD_BLOCKS")) target = atol(e);                       // tuning
-    int rpb = std::max(2, (int)cdiv((long)T2 * B, target));
+    rpb = std::max(2, (int)cdiv((long)T2 * B, target));
     rpb += rpb & 1;                                                                              // even: a block starts on an even conv0 row
-    dim3 grid(cdiv(T2, rpb), (unsigned)B), block(512);
+    grid = dim3(cdiv(T2, rpb), (unsigned)B);
+    return true;
+}
+// bytes of workspace the MFMA backward needs (0: it does not take this shape): one slab row of 20C f32 per workgroup
+int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C) {
+    dim3 grid; size_t sh; int rpb;
+    if (B * T * F == 0 || !stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb)) return 0;
+    return (int64_t)grid.x * grid.y * 20 * C * 4;
+}
+
+// 1: launched, 0: the shape is not for this kernel, -1: error (set)
+int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
+                           float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
+    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
+    dim3 grid; size_t sh; int rpb;
+    if (!stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb)) return 0;
+    const dim3 block(512);
+    // slab row: [dw0 9C | db0 C | dwd 9C | dbd C], added into the gradients in workgroup order after the kernel
+    const long rows = (long)grid.x * grid.y, dst = 20 * C;
+    float* sl = det_begin<float>(workspace, workspace_bytes, rows, dst, stream);
+    if (!sl) { sconf_set_error("sconf_sub_stage01_bwd: needs %ld bytes of workspace (sconf_sub_stage01_bwd_workspace)", rows * dst * 4); return -1; }
 #define LB(TX, NCB_) do { \
         if (sh > 64 * 1024) { static bool attr = false; if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_bwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } } \
-        hipLaunchKernelGGL((stage01_bwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, (const bf16*)dd1, dw0, db0, dwd, dbd, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb); } while (0)
+        hipLaunchKernelGGL((stage01_bwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, (const bf16*)dd1, sl, sl + 9 * C, sl + 10 * C, sl + 19 * C, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb, dst); } while (0)
     if (x_dtype == SCONF_F32) { if (C <= 256) LB(float, 1); else LB(float, 2); }
     else                      { if (C <= 256) LB(bf16, 1); else LB(bf16, 2); }
 #undef LB
+    det_finish<float>(sl, rows, dst, DetSegs<float>{{dw0, db0, dwd, dbd}, {0, 9 * C, 10 * C, 19 * C}, {9 * C, C, 9 * C, C}, 4}, stream);
     return 1;
 }
 

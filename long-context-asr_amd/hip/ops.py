@@ -34,6 +34,11 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """Scratch bytes for a kernel's fixed-order partial sums (torch's caching allocator; the library zeroes or writes it first)."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -349,7 +354,9 @@ def colsum_(x: torch.Tensor, out: torch.Tensor, alpha: float = 1.0) -> torch.Ten
     """out[n] += alpha * sum_m x[m, n]  (in place, f32)."""
     _chk(x, 'x'); _chk(out, 'out', torch.float32)
     N = x.shape[-1]; M = x.numel() // N
-    _lib.call('sconf_colsum', _p(x), _dt(x), _p(out), M, N, N, float(alpha), _stream())
+    nws = int(_lib.load().sconf_colsum_workspace(M, N))                 # row-block sums, added in a fixed order
+    ws = _workspace(nws, x.device) if nws else None
+    _lib.call('sconf_colsum', _p(x), _dt(x), _p(out), M, N, N, float(alpha), _p(ws), nws, _stream())
     return out
 
 
@@ -414,7 +421,9 @@ def glu_dwconv_fwd(g: torch.Tensor, lengths: Optional[torch.Tensor], w: torch.Te
     ks = w.numel() // d
     h = torch.empty(B * N, d, dtype=torch.bfloat16, device=g.device)
     stats = torch.zeros(2, d, dtype=torch.float64, device=g.device)
-    _lib.call('sconf_glu_dwconv_fwd', _p(g), _p(lengths), _p(w), _p(bias), _p(h), _p(stats), B, N, d, ks, _stream())
+    nws = int(_lib.load().sconf_glu_dwconv_fwd_workspace(B, N, d))     # per-workgroup statistics, added in a fixed order
+    ws = _workspace(nws, g.device)
+    _lib.call('sconf_glu_dwconv_fwd', _p(g), _p(lengths), _p(w), _p(bias), _p(h), _p(stats), _p(ws), nws, B, N, d, ks, _stream())
     return h, stats
 
 
@@ -448,8 +457,10 @@ def convmod_bwd(dy, h, g, lengths, w, brn_weight, coef, B: int, N: int, training
     bcoef = torch.empty(3, d, dtype=torch.float32, device=dy.device)
     dwt = torch.zeros(ks, d, dtype=torch.float32, device=dy.device)       # kernel accumulates the tap gradients as [k][d]
     cs = torch.zeros(2 * d, dtype=torch.float32, device=dy.device) if colsum else None
+    nws = int(_lib.load().sconf_convmod_bwd_workspace(B, N, d, ks, int(colsum)))   # per-workgroup sums, added in a fixed order
+    ws = _workspace(nws, dy.device)
     _lib.call('sconf_convmod_bwd', _p(dy), _p(h), _p(g), _p(lengths), _p(w), _p(brn_weight), _p(coef), _p(red), _p(bcoef), _p(dg),
-              _p(dwt), _p(dbias), _p(dbrn_weight), _p(dbrn_bias), _p(cs), B, N, d, ks, int(training), float(eps), _stream())
+              _p(dwt), _p(dbias), _p(dbrn_weight), _p(dbrn_bias), _p(cs), _p(ws), nws, B, N, d, ks, int(training), float(eps), _stream())
     dw.add_(dwt.t())
     return (dg, cs) if colsum else dg
 
@@ -488,7 +499,10 @@ def sub_dwconv_bwd(dout: torch.Tensor, w: torch.Tensor, pre_in: torch.Tensor, dw
     if colsum_into is not None:
         _chk(colsum_into, 'colsum_into', torch.float32)
         if colsum_into.numel() != Cc: raise ValueError('colsum_into must have one element per channel')
-    _lib.call('sconf_sub_dwconv_bwd', _p(dout), _p(w), _p(pre_in), _p(dpre), _p(dw), _p(dbias), _p(colsum_into), B, Ti, Fi, Cc, _stream())
+    nws = int(_lib.load().sconf_sub_dwconv_bwd_workspace(B, Ti, Fi, Cc, int(colsum_into is not None)))   # fixed-order sums
+    ws = _workspace(nws, dout.device)
+    _lib.call('sconf_sub_dwconv_bwd', _p(dout), _p(w), _p(pre_in), _p(dpre), _p(dw), _p(dbias), _p(colsum_into), _p(ws), nws,
+              B, Ti, Fi, Cc, _stream())
     return dpre
 
 
@@ -511,8 +525,10 @@ def sub_stage01_bwd_(dd1: torch.Tensor, x: torch.Tensor, w0, b0, wd, dw0, db0, d
     """Parameter gradients of the fused stage (accumulated in place) from dd1 (B,T4,F4,C) bf16."""
     _chk(dd1, 'dd1', torch.bfloat16); _chk(x, 'x')
     B, F, T = x.shape; Cc = dd1.shape[-1]
+    nws = int(_lib.load().sconf_sub_stage01_bwd_workspace(B, F, T, Cc))  # fixed-order gradient sums (MFMA kernel)
+    ws = _workspace(nws, dd1.device) if nws else None
     _lib.call('sconf_sub_stage01_bwd', _p(dd1), _p(x), _dt(x), _p(w0), _p(b0), _p(wd), _p(dw0), _p(db0), _p(dwd), _p(dbd),
-              B, F, T, Cc, _stream())
+              _p(ws), nws, B, F, T, Cc, _stream())
 
 
 def sub_silu_transpose(pre: torch.Tensor, ds: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -605,7 +621,9 @@ def ctc_bwd(log_probs, ws, nll, targets, input_lengths, target_lengths, grad_out
 def sumsq_(g: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out (f64 scalar tensor) += sum(g^2)."""
     _chk(g, 'g', torch.float32); _chk(out, 'out', torch.float64)
-    _lib.call('sconf_sumsq', _p(g), g.numel(), _p(out), _stream())
+    nws = int(_lib.load().sconf_sumsq_workspace(g.numel()))             # per-workgroup sums, added in a fixed order
+    ws = _workspace(nws, g.device) if nws else None
+    _lib.call('sconf_sumsq', _p(g), g.numel(), _p(out), _p(ws), nws, _stream())
     return out
 
 

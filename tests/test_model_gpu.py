@@ -308,6 +308,39 @@ def test_eval_mode_and_determinism():
     assert float((a.exp().sum(-1) - 1).abs().max()) < 1e-3
 
 
+def test_training_steps_are_bitwise_reproducible():
+    """Trainer.step three times, twice from the same seed: the losses, the gradients of every step, the parameters and the
+    BatchRenorm buffers are equal bit for bit.  Every reduction of the step (conv-module statistics and gradients, subsampler
+    weight gradients, column sums, CTC occupancies, gradient norm) runs in a fixed order; float atomics from many workgroups
+    would make them depend on arrival order, and MADGRAD amplifies such last-bit differences within a few steps.  The shape
+    spreads each of those reductions over many workgroups."""
+    from lcasr_amd.models.sconformer_xl import SCConformerXL
+    from lcasr_amd.train import Trainer, synthetic_batch
+    cfg = dict(vocab_size=4095, n_layers=2, d_model=768, n_heads=6, head_dim=128, subsampling_conv_channels=256, use_rotary=True,
+               rotary_base_freq=1500000, decoder_norm=True, self_conditioning=True, default_norm='layer_norm', bias_in_ff=False)
+
+    def run():
+        torch.manual_seed(12345)
+        m = SCConformerXL(**cfg).cuda().train()
+        tr = Trainer(m, lr=3e-3, clip_value=0.8, global_batch=4)
+        grads, step = [], tr.opt.step
+
+        def keep_grad(**kw):
+            grads.append(tr.opt.flat[0].grad.clone())
+            return step(**kw)
+        tr.opt.step = keep_grad
+        audio, lengths, targets, tl = synthetic_batch(4, 8192, cfg['vocab_size'], seed=0)
+        losses = [tr.step(audio, lengths, targets, tl).clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        return losses, grads, tr.opt.flat[0].data.clone(), {k: v.clone() for k, v in m.state_dict().items()}
+
+    (l0, g0, p0, s0), (l1, g1, p1, s1) = run(), run()
+    assert len(g0) == 3 and all(torch.equal(a, b) for a, b in zip(l0, l1)), ([float(a) for a in l0], [float(b) for b in l1])
+    assert all(torch.equal(a, b) for a, b in zip(g0, g1)), [i for i, (a, b) in enumerate(zip(g0, g1)) if not torch.equal(a, b)]
+    assert torch.equal(p0, p1), float((p0 - p1).abs().max())
+    assert all(torch.equal(s0[k], s1[k]) for k in s0), [k for k in s0 if not torch.equal(s0[k], s1[k])]
+
+
 def test_full_size_properties_c3_shape():
     """BASELINE config 3 shape (6L/768D/6H, T=16384, B=1): size-independent properties of the hot path."""
     from lcasr_amd.losses import CTCLoss
