@@ -133,8 +133,9 @@ int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, i
 /* zero rows n >= lengths[b] of x[B][N][d] in place (attention.py:511,546-547; convolution.py:109-110). */
 int sconf_mask_rows(void* x, int dtype, const int32_t* lengths, int64_t B, int64_t N, int64_t d, sconf_stream_t stream);
 
-/* Flash attention, bidirectional, head_dim 32 or 128; replaces FlashSelfAttention.forward(qkv[,key_padding_mask],
- * cu_seqlens, max_seqlen) = flash_attn_qkvpacked_func / flash_attn_varlen_qkvpacked_func (attention.py:200-257,
+/* Flash attention, bidirectional, head_dim 32, 64, 128 or 256 (64 and 256 from sconf_version() 200 on); replaces
+ * FlashSelfAttention.forward(qkv[,key_padding_mask], cu_seqlens, max_seqlen) = flash_attn_qkvpacked_func /
+ * flash_attn_varlen_qkvpacked_func (attention.py:200-257,
  * 527-535) and F.scaled_dot_product_attention (attention.py:541).  q,k,v,o: bf16 (B,N,H,D) views with element
  * strides {batch, token, head}; lengths: int32 [B] or NULL; window (-1 = unbounded); lse: f32 (B,H,N).
  * sconf_attn_bwd: delta is f32 scratch of 2*B*H*N floats (the dQ kernel, which runs first, leaves the row statistics of the

@@ -1,4 +1,4 @@
-// Flash-style bidirectional self-attention for gfx950, forward + backward, head_dim 32 or 128.
+// Flash-style bidirectional self-attention for gfx950, forward + backward, head_dim 32, 64, 128 or 256.
 // Replaces flash_attn_qkvpacked_func / flash_attn_varlen_qkvpacked_func + bert_padding un/pad
 // (attention.py:235-257, 527-535) and the CPU SDPA branch (attention.py:536-544):
 // non-causal softmax(QK^T/sqrt(D))V, optional key-padding via per-sample lengths (ragged batches
@@ -79,9 +79,20 @@ __device__ __forceinline__ BlkId decode_block(const AttnParams& p, int nx) {
 
 constexpr float RESCALE_LOG2 = 6.f;   // forward: rescale O / l only when a row's maximum has grown by more than 2^6 (see attn_fwd*_kernel)
 
+// The LDS image of a [rows][D] bf16 tile: 16-byte chunk ch of row `row` sits at chunk ch ^ swz<D>(row) of that row.  Every
+// writer (Stage, glds_tile*, dma_tile, tile_voff) and reader (tile_off) goes through this one formula.  What the readers need:
+//  (a) it depends on row & 15 only: a 16-row-aligned base adds linearly (LaneOffs);
+//  (b) swz(row + 8) == swz(row) ^ 2 for row & 15 < 8: frag_tr's second half is `trlo ^ 32`, 8 rows further;
+//  (c) the ds_read_b128 row reads (16 lanes of a group on 16 rows distinct mod 16, one chunk) and the ds_read_b64_tr_b16
+//      transposed reads (a 32-lane half on rows 4hh + 0..3, chunks 4db + 0..3) are conflict-free.
+// Bank rows are 256 bytes: D = 32 puts 4 rows in one, D = 64 two, D = 128 one, D = 256 half a row (only ch & 15 picks the bank).
+template <int D> __device__ __forceinline__ int swz(int row) {
+    if constexpr (D == 32) return (row >> 2) & 3;
+    else if constexpr (D == 64) return (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1) | ((row >> 2) & 1);
+    else return ((row & 3) << 2) | ((row >> 2) & 3);
+}
 template <int D> __device__ __forceinline__ int tile_off(int row, int ch) {
-    const int swz = (D == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
-    return row * (2 * D) + ((ch ^ swz) << 4);
+    return row * (2 * D) + ((ch ^ swz<D>(row)) << 4);
 }
 
 // ---- staging of a [ROWS][D] bf16 tile ---------------------------------------------------------
@@ -123,9 +134,8 @@ __device__ __forceinline__ void glds_tile(const bf16* base, long sn, int row0, i
         const int c = tid + 256 * i;
         if (CHUNKS % 256 == 0 || c < CHUNKS) {
             const int row = c / CPR, pos = c % CPR;
-            const int swz = (D == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
             const int gr = min(row0 + row, nrows_valid - 1);
-            __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz) * 8), (lptr)(lds + ((tid & ~63) + 256 * i) * 16), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz<D>(row)) * 8), (lptr)(lds + ((tid & ~63) + 256 * i) * 16), 16, 0, 0);
         }
     }
 }
@@ -141,9 +151,8 @@ __device__ __forceinline__ void glds_tile_n(const bf16* base, long sn, int row0,
     for (int i = 0; i < PER; ++i) {
         const int c = tid + NTHR * i;
         const int row = c / CPR, pos = c % CPR;
-        const int swz = (D == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
         const int gr = min(row0 + row, nrows_valid - 1);
-        __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz) * 8), (lptr)(lds + ((tid & ~63) + NTHR * i) * 16), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz<D>(row)) * 8), (lptr)(lds + ((tid & ~63) + NTHR * i) * 16), 16, 0, 0);
     }
 }
 template <int D, int ROWS>
@@ -186,9 +195,8 @@ __device__ __forceinline__ void dma_tile(const bf16* base, long sn, int row0, in
     for (int i = 0; i < PER; ++i) {
         const int c = tid + NTHR * i;
         const int row = c / CPR, pos = c % CPR;
-        const int swz = (D == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
         const int gr = min(row0 + row, nrows_valid - 1);
-        dma16_asm(base + (long)gr * sn + (pos ^ swz) * 8, wbase + (unsigned)(NTHR * i) * 16u);
+        dma16_asm(base + (long)gr * sn + (pos ^ swz<D>(row)) * 8, wbase + (unsigned)(NTHR * i) * 16u);
     }
 }
 
@@ -214,8 +222,7 @@ template <int D, int NTHR> __device__ __forceinline__ unsigned tile_voff(long sn
     constexpr int CPR = D / 8;
     static_assert((NTHR / CPR) % 16 == 0, "a pass must be whole groups of 16 rows (the swizzle period)");
     const int row = tid / CPR, pos = tid % CPR;
-    const int swz = (D == 128) ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((row >> 2) & 3);
-    return (unsigned)(row * sn * 2 + ((pos ^ swz) << 4));
+    return (unsigned)(row * sn * 2 + ((pos ^ swz<D>(row)) << 4));
 }
 // NP pieces of a tile: piece k reads srd base + soff + k * sstep + voff and lands at lds_wave_base + k * LSTEP + lane * 16
 #define SCONF_DMA_FIRST "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
@@ -332,21 +339,21 @@ template <int D> __device__ __forceinline__ void store_t(const f32x16 (&acc)[D /
 // The same store with the transpose of the NeoX rotation applied first: acc is the gradient with respect to the ROTATED q (or k) of
 // row n; what is stored is the gradient with respect to the unrotated one (rotary_emb.py:61-73):
 //     g[d] = g'[d] cos + g'[d + D/2] sin,   g[d + D/2] = g'[d + D/2] cos - g'[d] sin        (d < D/2, cos/sin at (n, d)).
-// Both partners sit in the same lane: d = 32 db + acc_row(r, hh), so d + 64 is accumulator block db + 2 (D = 128) and d + 16 is
-// register r + 8 (D = 32).  This replaces the separate (dq, dk, dv) -> dqkv rotary pass over the activations.
+// Both partners sit in the same lane: d = 32 db + acc_row(r, hh), so for D >= 64 d + D/2 is accumulator block db + D/64 (same
+// register), and for D = 32 d + 16 is register r + 8.  This replaces the separate (dq, dk, dv) -> dqkv rotary pass over the activations.
 template <int D> __device__ __forceinline__ void store_t_rot(f32x16 (&acc)[D / 32], bf16* dst_row, float sc, int hh, const float* cs, const float* sn) {
-    if constexpr (D == 128) {
+    if constexpr (D >= 64) {
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+        for (int db = 0; db < D / 64; ++db)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 float c[4], s[4];
                 load4(cs + db * 32 + 8 * r4 + 4 * hh, c); load4(sn + db * 32 + 8 * r4 + 4 * hh, s);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float a = acc[db][4 * r4 + e], b = acc[db + 2][4 * r4 + e];
+                    const float a = acc[db][4 * r4 + e], b = acc[db + D / 64][4 * r4 + e];
                     acc[db][4 * r4 + e] = a * c[e] + b * s[e];
-                    acc[db + 2][4 * r4 + e] = b * c[e] - a * s[e];
+                    acc[db + D / 64][4 * r4 + e] = b * c[e] - a * s[e];
                 }
             }
     } else {
@@ -369,7 +376,7 @@ template <int D> __device__ __forceinline__ void store_t_rot(f32x16 (&acc)[D / 3
 // forward: grid (ceil(N/128), H, B), 4 waves x 32 query rows, 64-key tiles
 // =============================================================================================
 template <int D>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_fwd_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TB = 64 * 2 * D;                     // bytes of one 64-row tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
@@ -914,7 +921,7 @@ __global__ void attn_delta_kernel(const AttnParams p) {
 // backward dK/dV: grid (ceil(N/128), H, B); each wave owns 32 keys, sweeps 32-row query tiles
 // =============================================================================================
 template <int D>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_bwd_dkdv_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TB = 32 * 2 * D;                     // Q tile / dO tile bytes (32 rows)
     constexpr int SB = 2 * TB + 256;                   // one stage: Q | dO | lse2[32] | delta[32]
@@ -1184,7 +1191,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv8_kernel(const AttnParams p)
 // backward dQ: grid (ceil(N/128), H, B); each wave owns 32 queries, sweeps 64-key tiles
 // =============================================================================================
 template <int D>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnParams p) {
+__global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_bwd_dq_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TB = 64 * 2 * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
@@ -1422,17 +1429,32 @@ static void stamp_report(const char* what, unsigned long long* sbuf, long nwg, d
 }
 #endif
 
+// dynamic LDS of the 4-wave kernels: forward / dQ = 2 stages x (K | V) x 64 rows; dK/dV = 2 stages x (Q | dO 32 rows + statistics)
+// + the workgroup's 128 V rows.  D = 256: 128 KiB and 131584 B - one workgroup per CU (hence their launch bounds).
+template <int D> constexpr int fwd_lds() { return 4 * 64 * 2 * D; }
+template <int D> constexpr int dkdv_lds() { return 2 * (2 * 32 * 2 * D + 256) + 128 * 2 * D; }
+template <int D> void set_lds_attrs_d() {
+    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd_lds<D>());
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd_lds<D>());
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, dkdv_lds<D>());
+}
 void set_lds_attrs() {
     static bool done = false;
     if (done) return;
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 256);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 256);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (2 * 32 * 256 + 256) + 128 * 256);
+    set_lds_attrs_d<64>(); set_lds_attrs_d<128>(); set_lds_attrs_d<256>();
     done = true;
+}
+// the 4-wave kernels for one head_dim
+template <int D> void launch_fwd4(const AttnParams& p, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((attn_fwd_kernel<D>), grid, dim3(256), fwd_lds<D>(), stream, p);
+}
+template <int D> void launch_bwd4(const AttnParams& p, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<D>), grid, dim3(256), fwd_lds<D>(), stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D>), grid, dim3(256), dkdv_lds<D>(), stream, p);
 }
 
 int check_common(const char* fn, int64_t B, int64_t N, int64_t H, int64_t D, const int64_t* strides, int nstr) {
-    if (!(D == 32 || D == 128)) return sconf_set_error("%s: head_dim %ld not supported (32 or 128)", fn, (long)D);
+    if (!(D == 32 || D == 64 || D == 128 || D == 256)) return sconf_set_error("%s: head_dim %ld not supported (32, 64, 128 or 256)", fn, (long)D);
     if (B <= 0 || N <= 0 || H <= 0) return sconf_set_error("%s: empty problem", fn);
     if (B > 65535 || H > 65535) return sconf_set_error("%s: B and H must be <= 65535", fn);
     for (int i = 0; i < nstr; ++i) if (strides[i] % 8 != 0) return sconf_set_error("%s: strides must be multiples of 8 elements", fn);
@@ -1458,7 +1480,7 @@ SCONF_API int sconf_attn_fwd(const void* q, const void* k, const void* v, void* 
     p.v_sb = v_strides[0]; p.v_sn = v_strides[1]; p.v_sh = v_strides[2];
     p.o_sb = o_strides[0]; p.o_sn = o_strides[1]; p.o_sh = o_strides[2];
     p.B = (int)B; p.N = (int)N; p.H = (int)H; p.win_left = win_left; p.win_right = win_right; p.scale = scale;
-    dim3 grid((unsigned)(cdiv(N, 128) * H * B)), block(256);
+    dim3 grid((unsigned)(cdiv(N, 128) * H * B));
     { const char* ex = getenv("SCONF_ATTN_XCD"); p.xcd_remap = !(ex && ex[0] == '0'); }       // A/B switch, read per call
     set_lds_attrs();
     const char* e8 = getenv("SCONF_ATTN_WIDE");            // "0" keeps the 4-wave kernels (A/B, tests); read per call
@@ -1499,8 +1521,10 @@ SCONF_API int sconf_attn_fwd(const void* q, const void* k, const void* v, void* 
             }
         }
 #endif
-    } else if (D == 128) hipLaunchKernelGGL((attn_fwd_kernel<128>), grid, block, 4 * 64 * 256, stream, p);
-    else          hipLaunchKernelGGL((attn_fwd_kernel<32>), grid, block, 4 * 64 * 64, stream, p);
+    } else if (D == 128) launch_fwd4<128>(p, grid, stream);
+    else if (D == 256) launch_fwd4<256>(p, grid, stream);
+    else if (D == 64) launch_fwd4<64>(p, grid, stream);
+    else launch_fwd4<32>(p, grid, stream);
     SCONF_LAUNCH_OK("sconf_attn_fwd");
     return 0;
 }
@@ -1552,7 +1576,7 @@ SCONF_API int sconf_attn_bwd(const void* q, const void* k, const void* v, const 
             { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dQ chain", "wait+barrier"}; stamp_report("dq8 (unit = 32 keys)", p.stamps, cdiv(N, 256) * H * B, (double)((N + 31) / 32), 5, nm, stream); }
 #endif
         } else
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), grid, block, 4 * 64 * 256, stream, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), grid, block, fwd_lds<128>(), stream, p);
         const char* e8 = getenv("SCONF_ATTN_DKDV8");           // "0" keeps the 4-wave dK/dV kernel (A/B, tests); read per call
         const bool wide = !(e8 && e8[0] == '0');
         if (wide && N >= 256 && fits32) {
@@ -1567,11 +1591,10 @@ SCONF_API int sconf_attn_bwd(const void* q, const void* k, const void* v, const 
             { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dV|dK chains", "wait+barrier"}; stamp_report("dkdv8 (unit = 32 queries)", p.stamps, cdiv(N, 256) * H * B, (double)((N + 31) / 32), 5, nm, stream); }
 #endif
         } else
-            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<128>), grid, block, 2 * (2 * 32 * 256 + 256) + 128 * 256, stream, p);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<32>), grid, block, 4 * 64 * 64, stream, p);
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<32>), grid, block, 2 * (2 * 32 * 64 + 256) + 128 * 64, stream, p);
-    }
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<128>), grid, block, dkdv_lds<128>(), stream, p);
+    } else if (D == 256) launch_bwd4<256>(p, grid, stream);
+    else if (D == 64) launch_bwd4<64>(p, grid, stream);
+    else launch_bwd4<32>(p, grid, stream);
     SCONF_LAUNCH_OK("sconf_attn_bwd");
     return 0;
 }

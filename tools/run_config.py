@@ -1,5 +1,5 @@
 """Run a few training steps of a BASELINE.json config on one GPU and print ms/step, frames/s, loss, peak memory.
-usage: python tools/run_config.py {c1|c2|c3|c4|c5} [batch] [steps]"""
+usage: python tools/run_config.py {c1|c2|c3|c4|c5|h12|h3} [batch] [steps]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,6 +11,9 @@ CFG = {
     'c1': (dict(base, n_layers=6, d_model=256, n_heads=8, head_dim=32, subsampling_conv_channels=256), 1024, 2),
     'c2': (dict(base, n_layers=6, d_model=768, n_heads=6, head_dim=128, subsampling_conv_channels=256), 1024, 64),
     'c3': (dict(base, n_layers=6, d_model=768, n_heads=6, head_dim=128, subsampling_conv_channels=256), 16384, 16),
+    # the paper's head-count sweep at c3's shape: exp_set_rot_12h.yaml (12 x 64) and exp_set_rot_3h.yaml (3 x 256)
+    'h12': (dict(base, n_layers=6, d_model=768, n_heads=12, head_dim=64, subsampling_conv_channels=256), 16384, 16),
+    'h3': (dict(base, n_layers=6, d_model=768, n_heads=3, head_dim=256, subsampling_conv_channels=256), 16384, 16),
     # exp/configs/paper_templates/exp_set_seq_rotary_base_9l.yaml: per-layer checkpointing + ff_checkpoint_lvl 2
     'c4': (dict(base, n_layers=9, d_model=768, n_heads=6, head_dim=128, subsampling_conv_channels=256, checkpoint_every_n_layers=1, ff_checkpoint_lvl=2), 16384, 16),
     # exp_set_seq_rotary_base_3l_2048.yaml
