@@ -61,8 +61,8 @@ int sconf_gemm_softmax_bwd(const void* dy, const void* Wt, const void* probs, co
 int sconf_rowdot(const void* a, const void* b, const float* bias, float* out, int64_t M, int64_t d, int64_t lda, int64_t ldb,
                  sconf_stream_t stream);
 int sconf_gemm_num_splits(int64_t K, int split_k);
-/* Which kernel sconf_gemm_bf16 runs for a problem (bookkeeping for benchmarks): 0 = 128x128-tile kernel, 1 / 2 = 256-row NT
- * kernel with 256 / 192-wide tiles, 3 = 256x256 TN kernel; -1 = invalid arguments. */
+/* Which kernel sconf_gemm_bf16 runs for a problem (bookkeeping for benchmarks): 0 = 128x128-tile kernel, 1 = 256x256 NT
+ * kernel, 2 = 256x192 NT kernel (three phases per K-tile), 3 = 256x256 TN kernel; -1 = invalid arguments. */
 int sconf_gemm_variant(int layout, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int split_k, int act,
                        int has_resid, int has_pre);
 int sconf_splitk_reduce(const float* slab, float* out, int64_t splits, int64_t n, int accumulate, sconf_stream_t stream);

@@ -38,7 +38,6 @@ struct AttnParams {
     int B, N, H;
     int win_left, win_right;          // -1 = unbounded
     float scale;                      // 1/sqrt(D)
-    int xcd_remap;                    // 1: XCD-contiguous workgroup order (decode_block)
     const float *rot_cos, *rot_sin;   // backward: (N, D/2) rotary tables or null - dq, dk are returned as gradients of the UNROTATED q, k
     unsigned long long* stamps;       // diagnostic builds only (-DSCONF_ATTN_STAMP): per (workgroup, wave) segment cycle sums
 };
@@ -65,11 +64,8 @@ struct AttnParams {
 struct BlkId { int b, h, x; };
 __device__ __forceinline__ BlkId decode_block(const AttnParams& p, int nx) {
     const int total = nx * p.H * p.B, v = blockIdx.x;
-    int lid = v;
-    if (p.xcd_remap) {
-        const int q = total >> 3, r = total & 7, xcd = v & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-    }
+    const int q = total >> 3, r = total & 7, xcd = v & 7;
+    const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
     BlkId o;
     o.x = lid % nx;
     const int bh = lid / nx;
@@ -80,7 +76,7 @@ __device__ __forceinline__ BlkId decode_block(const AttnParams& p, int nx) {
 constexpr float RESCALE_LOG2 = 6.f;   // forward: rescale O / l only when a row's maximum has grown by more than 2^6 (see attn_fwd*_kernel)
 
 // The LDS image of a [rows][D] bf16 tile: 16-byte chunk ch of row `row` sits at chunk ch ^ swz<D>(row) of that row.  Every
-// writer (Stage, glds_tile*, dma_tile, tile_voff) and reader (tile_off) goes through this one formula.  What the readers need:
+// writer (glds_tile, dma_tile, tile_voff) and reader (tile_off) goes through this one formula.  What the readers need:
 //  (a) it depends on row & 15 only: a 16-row-aligned base adds linearly (LaneOffs);
 //  (b) swz(row + 8) == swz(row) ^ 2 for row & 15 < 8: frag_tr's second half is `trlo ^ 32`, 8 rows further;
 //  (c) the ds_read_b128 row reads (16 lanes of a group on 16 rows distinct mod 16, one chunk) and the ds_read_b64_tr_b16
@@ -94,31 +90,6 @@ template <int D> __device__ __forceinline__ int swz(int row) {
 template <int D> __device__ __forceinline__ int tile_off(int row, int ch) {
     return row * (2 * D) + ((ch ^ swz<D>(row)) << 4);
 }
-
-// ---- staging of a [ROWS][D] bf16 tile ---------------------------------------------------------
-template <int D, int ROWS> struct Stage {
-    static constexpr int CPR = D / 8, CHUNKS = ROWS * CPR, PER = (CHUNKS + 255) / 256;
-    uint4 r[PER];
-    __device__ __forceinline__ void gload(const bf16* base, long sn, int row0, int nrows_valid, int tid) {
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int c = tid + 256 * i;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (c < CHUNKS) {
-                const int row = c / CPR, ch = c % CPR;
-                if (row0 + row < nrows_valid) v = *reinterpret_cast<const uint4*>(base + (long)(row0 + row) * sn + ch * 8);
-            }
-            r[i] = v;
-        }
-    }
-    __device__ __forceinline__ void lstore(char* s, int tid) const {
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int c = tid + 256 * i;
-            if (c < CHUNKS) *reinterpret_cast<uint4*>(s + tile_off<D>(c / CPR, c % CPR)) = r[i];
-        }
-    }
-};
 
 // ---- LDS-DMA staging of a [ROWS][D] bf16 tile (global_load_lds_dwordx4): no staging VGPRs, no ds_write, no guards --
 // LDS destination is linear (wave base + lane*16), so the tile_off swizzle is applied to the per-lane SOURCE chunk and
@@ -138,26 +109,6 @@ __device__ __forceinline__ void glds_tile(const bf16* base, long sn, int row0, i
             __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz<D>(row)) * 8), (lptr)(lds + ((tid & ~63) + 256 * i) * 16), 16, 0, 0);
         }
     }
-}
-
-// the same for workgroups of NTHR threads (tile = whole passes of the workgroup)
-template <int D, int ROWS, int NTHR>
-__device__ __forceinline__ void glds_tile_n(const bf16* base, long sn, int row0, int nrows_valid, char* lds, int tid) {
-    constexpr int CPR = D / 8, CHUNKS = ROWS * CPR, PER = CHUNKS / NTHR;
-    static_assert(CHUNKS % NTHR == 0, "tile must be whole passes of the workgroup");
-    typedef const __attribute__((address_space(1))) void* gptr;
-    typedef __attribute__((address_space(3))) void* lptr;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int c = tid + NTHR * i;
-        const int row = c / CPR, pos = c % CPR;
-        const int gr = min(row0 + row, nrows_valid - 1);
-        __builtin_amdgcn_global_load_lds((gptr)(base + (long)gr * sn + (pos ^ swz<D>(row)) * 8), (lptr)(lds + ((tid & ~63) + NTHR * i) * 16), 16, 0, 0);
-    }
-}
-template <int D, int ROWS>
-__device__ __forceinline__ void glds_tile512(const bf16* base, long sn, int row0, int nrows_valid, char* lds, int tid) {
-    glds_tile_n<D, ROWS, 512>(base, sn, row0, nrows_valid, lds, tid);
 }
 
 // ---- LDS-DMA issued from inline asm ----------------------------------------------------------------------------------
@@ -184,7 +135,7 @@ __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
 }
-// [ROWS][D] bf16 tile by asm DMA, NTHR threads; same swizzled image as glds_tile_n
+// [ROWS][D] bf16 tile by asm DMA, NTHR threads; same swizzled image as glds_tile
 // `lds` = byte address of the tile in LDS as a wave-uniform (scalar) value
 template <int D, int ROWS, int NTHR>
 __device__ __forceinline__ void dma_tile(const bf16* base, long sn, int row0, int nrows_valid, unsigned lds, int tid) {
@@ -233,13 +184,13 @@ template <int NP, int LSTEP> __device__ __forceinline__ void dma_pieces(srd_t sr
     unsigned keep;
     if constexpr (NP == 8)
         asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory");
+                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
     else if constexpr (NP == 4)
         asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory");
+                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
     else
         asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory");
+                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
 }
 // A [ROWS][128] tile staged by a 512-thread workgroup = ROWS / 32 passes of 8 wave pieces.  Who issues them: every wave its own
 // piece of each pass, or - LOADERS - waves 0-3 only, each also the piece of wave w + 4 (16 rows further down: same swizzle, the
@@ -304,7 +255,7 @@ template <int D> __device__ __forceinline__ void load_bfrags(bf16x8 (&f)[D / 16]
 // delta[q] = sum_d dO[q][d] O[q][d] for this lane's query (lane & 31), from the dO fragments the dQ kernels hold anyway and O
 // fragments loaded the same way (each half-wave holds half of the d range: one cross-half exchange).  The dQ kernels run FIRST in
 // the backward, keep delta in a register for themselves and write it out for the dK/dV kernel: the separate delta pass
-// (round 1: attn_delta_kernel, 0.14 ms per layer at B = 128) is gone.
+// of round 1 (0.14 ms per layer at B = 128) is gone.
 template <int D> __device__ __forceinline__ float delta_from_frags(const bf16x8 (&gf)[D / 16], const bf16* op, long o_sn, int row0, int nvalid, int lane) {
     bf16x8 of[D / 16];
     load_bfrags<D>(of, op, o_sn, row0, nvalid, lane);
@@ -486,155 +437,11 @@ __global__ __launch_bounds__(256, D == 256 ? 1 : 2) void attn_fwd_kernel(const A
     }
 }
 
-// 8-wave form of the forward (D = 128): 256 queries per workgroup, 128-key stages shared by 8 waves.
-template <int D>
-__global__ __launch_bounds__(512) void attn_fwd8_kernel(const AttnParams p) {
-    constexpr int KT = 128;                            // keys per stage, consumed as two 64-key halves
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int TB = KT * 2 * D;                     // bytes of one stage tile
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
-    const BlkId bid = decode_block(p, (p.N + 255) / 256);
-    const int b = bid.b, h = bid.h, qb0 = bid.x * 256, q0 = qb0 + wave * 32;
-    const int len = p.lengths ? p.lengths[b] : p.N;
-    const bf16* qp = p.q + b * p.q_sb + h * p.q_sh;
-    const bf16* kp = p.k + b * p.k_sb + h * p.k_sh;
-    const bf16* vp = p.v + b * p.v_sb + h * p.v_sh;
-    const int qi = q0 + (lane & 31);
-    const float c = p.scale * 1.4426950408889634f;
-
-    bf16x8 qf[D / 16];
-    load_bfrags<D>(qf, qp, p.q_sn, q0, p.N, lane);
-    const LaneOffs<D> L(lane);
-
-    const int kv_lo = p.win_left < 0 ? 0 : max(0, qb0 - p.win_left);
-    const int kv_hi = min(len, p.win_right < 0 ? len : qb0 + 256 + p.win_right);
-    const int t_lo = kv_lo / KT, t_hi = (kv_hi + KT - 1) / KT;
-    const bool windowed = p.win_left >= 0 || p.win_right >= 0;
-
-    f32x16 o[D / 32];
-#pragma unroll
-    for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-    auto issue = [&](int t, int buf) {                     // K | V stage by asm-issued LDS-DMA (invisible to hipcc's vmcnt bookkeeping)
-        const int tid_ = opaque(tid);                      // offsets recomputed per stage: kept live across the loop they would be spilled
-        dma_tile<D, KT, 512>(kp, p.k_sn, t * KT, p.N, lds0 + (unsigned)(buf * 2 * TB), tid_);
-        dma_tile<D, KT, 512>(vp, p.v_sn, t * KT, p.N, lds0 + (unsigned)(buf * 2 * TB + TB), tid_);
-    };
-    if (t_lo < t_hi) issue(t_lo, 0);
-    pin_frags(qf);
-    dma_wait_all();
-    __syncthreads();
-    for (int t = t_lo; t < t_hi; ++t) {
-        const int cur = (t - t_lo) & 1;
-        const char* sK = smem + cur * 2 * TB;
-        const char* sV = sK + TB;
-        if (t + 1 < t_hi) issue(t + 1, cur ^ 1);             // next K/V tile streams into the other buffer during this tile
-        for (int half = 0; half < KT / 64; ++half) {
-        const int kv0 = t * KT + half * 64;
-        if (kv0 >= kv_hi) break;                           // uniform: the second half of the last stage may be past the keys
-        const char* sKh = sK + half * 64 * 2 * D;
-        const char* sVh = sV + half * 64 * 2 * D;
-        f32x16 s[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-        {   // S^T = K Q^T: 16 (K row fragment, MFMA) pairs, fragments requested PF pairs ahead.  Left alone hipcc reuses ONE
-            // destination register set (read -> lgkmcnt(0) -> MFMA, the LDS latency exposed 16 times); the order is pinned with
-            // sched_group_barrier (mask 0x100 = LDS read, 0x008 = MFMA).
-            constexpr int NP = 2 * (D / 16), PF = 3;
-            bf16x8 ka[NP];
-#pragma unroll
-            for (int i = 0; i < PF; ++i) ka[i] = frag_row<D>(sKh, L, (i / (D / 16)) * 32, i % (D / 16));
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                if (i + PF < NP) ka[i + PF] = frag_row<D>(sKh, L, ((i + PF) / (D / 16)) * 32, (i + PF) % (D / 16));
-                s[i / (D / 16)] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[i], qf[i % (D / 16)], s[i / (D / 16)], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
-#pragma unroll
-            for (int i = 0; i < NP - PF; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, PF, 0);
-        }
-        if (kv0 + 64 > kv_hi || windowed) {
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kv0 + kt * 32 + acc_row(r, hh);
-                    bool ok = key < len;
-                    if (p.win_left >= 0) ok = ok && key >= qi - p.win_left;
-                    if (p.win_right >= 0) ok = ok && key <= qi + p.win_right;
-                    if (!ok) s[kt][r] = -INFINITY;
-                }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // Deferred rescale: m is the reference point of the exponentials, not necessarily the running maximum.  It moves (and
-        // O, l are rescaled: 64 + 1 multiplies per lane) only when some row of the wave has outgrown it by more than 2^RESCALE_LOG2;
-        // until then P <= 2^RESCALE_LOG2 instead of <= 1, which costs nothing (bf16 P keeps its relative precision, O and l stay
-        // far inside f32 range) and O / l at the end is the same quotient.  The softmax VALU work is as long as the tile's
-        // MFMAs here, so the skipped rescale is time, not just instructions.
-        if (__any((mx - m) * c > RESCALE_LOG2)) {            // wave-uniform; also the first tile of every row (m = -inf)
-            const float mn = fmaxf(m, mx);
-            const float alpha = (mn == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f((m - mn) * c);
-            l *= alpha;
-            m = mn;
-#pragma unroll
-            for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-        }
-        const float mc = (m == -INFINITY) ? 0.f : m * c;
-        float rs = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { const float e = __builtin_amdgcn_exp2f(s[kt][r] * c - mc); s[kt][r] = e; rs += e; }
-        l += rs;
-        bf16x8 pf[2][2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) { pf[kt][0] = pack8(s[kt], 0); pf[kt][1] = pack8(s[kt], 1); }
-        {   // O^T += V^T P^T: 16 (transposed V fragment = 2 tr reads, MFMA) pairs, same pinned pipeline
-            constexpr int NP = 4 * (D / 32), PF = 2;
-            bf16x8 va[NP];
-#pragma unroll
-            for (int i = 0; i < PF; ++i) va[i] = frag_tr<D>(sVh, L, ((i >> 1) & 1) * 32 + 16 * (i & 1), i >> 2);
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                if (i + PF < NP) { const int j = i + PF; va[j] = frag_tr<D>(sVh, L, ((j >> 1) & 1) * 32 + 16 * (j & 1), j >> 2); }
-                o[i >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[i], pf[(i >> 1) & 1][i & 1], o[i >> 2], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * PF, 0);
-#pragma unroll
-            for (int i = 0; i < NP - PF; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, PF, 0);
-        }
-        }
-        dma_wait_all();                                      // the next stage has landed (issued a stage of MFMAs ago)
-        __syncthreads();
-    }
-    const float lt = l + __shfl_xor(l, 32, 64);
-    if (qi < p.N) {
-        const bool live = qi < len && lt > 0.f;
-        const float inv = live ? 1.f / lt : 0.f;
-        store_t<D>(o, p.o + b * p.o_sb + (long)qi * p.o_sn + h * p.o_sh, inv, hh);
-        if (hh == 0 && p.lse) p.lse[((long)b * p.H + h) * p.N + qi] = live ? (m * c + __log2f(lt)) * 0.6931471805599453f : INFINITY;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // Round 3: the 8-wave forward, software-pipelined inside the wave, without a running maximum.
 //
-// In-kernel stamps of the round-2 kernel above (B = 128, N = 2048; cycles per 64-key half-tile, waves 0-3 / waves 4-7):
+// In-kernel stamps of the round-2 8-wave kernel (running maximum per tile; retired, see DESIGN), B = 128, N = 2048, cycles per
+// 64-key half-tile, waves 0-3 / waves 4-7:
 //   DMA issue 474 / 990, S chain 742 / 1175, softmax 705 / 921, PV chain 635 / 709, stage barrier 1304 / 66  (sum 3930 for
 //   2048 cycles of MFMA work per SIMD).  Three things, in that order:
 //  (1) an LDS-DMA piece costs the issuing wave 75-180 cycles, and the younger half of the workgroup (waves 4-7 lose every
@@ -892,29 +699,6 @@ __global__ __launch_bounds__(512) void attn_fwd8p_kernel(const AttnParams p) {
         store_t<D>(o, p.o + b * p.o_sb + (long)qi * p.o_sn + h * p.o_sh, inv, hh);
         if (hh == 0 && p.lse) p.lse[((long)b * p.H + h) * p.N + qi] = live ? (mfin + __log2f(lt)) * 0.6931471805599453f : INFINITY;
     }
-}
-
-// delta[b][h][n] = sum_d dO * O
-template <int D>
-__global__ void attn_delta_kernel(const AttnParams p) {
-    constexpr int LPR = D / 8;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long rows = (long)p.B * p.N * p.H;
-    const long row = idx / LPR;
-    const int ch = (int)(idx % LPR);
-    float acc = 0.f;
-    long bb = 0, n = 0, hd = 0;
-    if (row < rows) {
-        hd = row % p.H; n = (row / p.H) % p.N; bb = row / ((long)p.H * p.N);
-        float a[8], g[8];
-        load8(p.o + bb * p.o_sb + n * p.o_sn + hd * p.o_sh + ch * 8, a);
-        load8(p.dout + bb * p.do_sb + n * p.do_sn + hd * p.do_sh + ch * 8, g);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc += a[e] * g[e];
-    }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (row < rows && ch == 0) p.delta[(bb * p.H + hd) * p.N + n] = acc;
 }
 
 // =============================================================================================
@@ -1433,6 +1217,9 @@ static void stamp_report(const char* what, unsigned long long* sbuf, long nwg, d
 // + the workgroup's 128 V rows.  D = 256: 128 KiB and 131584 B - one workgroup per CU (hence their launch bounds).
 template <int D> constexpr int fwd_lds() { return 4 * 64 * 2 * D; }
 template <int D> constexpr int dkdv_lds() { return 2 * (2 * 32 * 2 * D + 256) + 128 * 2 * D; }
+// the 8-wave kernels (D = 128): forward / dQ = 2 stages x (K | V) x 128 rows; dK/dV = 2 stages x (Q | dO 64 rows + statistics)
+// + the workgroup's 256 V rows
+constexpr int FWD8_LDS = 4 * 128 * 256, DKDV8_LDS = 2 * (2 * 64 * 256 + 512) + 256 * 256;
 template <int D> void set_lds_attrs_d() {
     (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd_lds<D>());
     (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, fwd_lds<D>());
@@ -1442,6 +1229,9 @@ void set_lds_attrs() {
     static bool done = false;
     if (done) return;
     set_lds_attrs_d<64>(); set_lds_attrs_d<128>(); set_lds_attrs_d<256>();
+    (void)hipFuncSetAttribute((const void*)attn_fwd8p_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD8_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, FWD8_LDS);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, DKDV8_LDS);
     done = true;
 }
 // the 4-wave kernels for one head_dim
@@ -1459,6 +1249,17 @@ int check_common(const char* fn, int64_t B, int64_t N, int64_t H, int64_t D, con
     if (B > 65535 || H > 65535) return sconf_set_error("%s: B and H must be <= 65535", fn);
     for (int i = 0; i < nstr; ++i) if (strides[i] % 8 != 0) return sconf_set_error("%s: strides must be multiples of 8 elements", fn);
     return 0;
+}
+
+// The 8-wave kernels take D = 128 from N = 256 on, when the first nviews views of `strides` ((stride_b, stride_n, stride_h) each)
+// fit a (batch, head) slice in 32-bit byte offsets: they address it through a buffer descriptor.  SCONF_ATTN_WIDE=0 keeps the
+// 4-wave kernels (tests compare the two); read per call.
+bool use_wide(int64_t D, int64_t N, const int64_t* strides, int nviews) {
+    const char* e = getenv("SCONF_ATTN_WIDE");
+    if (D != 128 || N < 256 || (e && e[0] == '0')) return false;
+    int64_t smax = 0;
+    for (int j = 0; j < nviews; ++j) smax = std::max(smax, strides[3 * j + 1]);
+    return (N - 1) * smax * 2 + 2 * D < (1L << 32);
 }
 
 }  // namespace
@@ -1480,46 +1281,16 @@ SCONF_API int sconf_attn_fwd(const void* q, const void* k, const void* v, void* 
     p.v_sb = v_strides[0]; p.v_sn = v_strides[1]; p.v_sh = v_strides[2];
     p.o_sb = o_strides[0]; p.o_sn = o_strides[1]; p.o_sh = o_strides[2];
     p.B = (int)B; p.N = (int)N; p.H = (int)H; p.win_left = win_left; p.win_right = win_right; p.scale = scale;
-    dim3 grid((unsigned)(cdiv(N, 128) * H * B));
-    { const char* ex = getenv("SCONF_ATTN_XCD"); p.xcd_remap = !(ex && ex[0] == '0'); }       // A/B switch, read per call
     set_lds_attrs();
-    const char* e8 = getenv("SCONF_ATTN_WIDE");            // "0" keeps the 4-wave kernels (A/B, tests); read per call
-    // the 8-wave kernels address a (batch, head) slice through a buffer descriptor: 32-bit byte offsets
-    const bool fits32 = (N - 1) * std::max(std::max(k_strides[1], v_strides[1]), q_strides[1]) * 2 + 2 * D < (1L << 32);
-    const bool wide = !(e8 && e8[0] == '0') && N >= 256 && fits32;
-    if (D == 128 && wide) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_fwd8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256);
-            (void)hipFuncSetAttribute((const void*)attn_fwd8p_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256);
-            attr_set = true;
-        }
-        const char* erc = getenv("SCONF_ATTN_RC");         // "0": the round-2 kernel (running maximum per tile); A/B and tests, read per call
-#ifdef SCONF_ATTN_STAMP
+    const dim3 grid((unsigned)(cdiv(N, 128) * H * B));
+    if (use_wide(D, N, all, 3)) {                          // q, k, v
         const long nwg = cdiv(N, 256) * H * B;
-        static unsigned long long* sbuf = nullptr; static long scap = 0;
-        if (scap < nwg * 64) { if (sbuf) (void)hipFree(sbuf); (void)hipMalloc(&sbuf, nwg * 64 * 8); scap = nwg * 64; }
-        (void)hipMemsetAsync(sbuf, 0, nwg * 64 * 8, stream);
-        p.stamps = sbuf;
-#endif
-        if (erc && erc[0] == '0') hipLaunchKernelGGL((attn_fwd8_kernel<128>), dim3((unsigned)(cdiv(N, 256) * H * B)), dim3(512), 4 * 128 * 256, stream, p);
-        else hipLaunchKernelGGL((attn_fwd8p_kernel<128>), dim3((unsigned)(cdiv(N, 256) * H * B)), dim3(512), 4 * 128 * 256, stream, p);
 #ifdef SCONF_ATTN_STAMP
-        if (getenv("SCONF_ATTN_STAMP_PRINT")) {
-            (void)hipStreamSynchronize(stream);
-            std::vector<unsigned long long> hb(nwg * 64);
-            (void)hipMemcpy(hb.data(), sbuf, nwg * 64 * 8, hipMemcpyDeviceToHost);
-            double sums[2][8] = {};
-            for (long w = 0; w < nwg * 8; ++w) for (int i = 0; i < 8; ++i) sums[(w & 7) >= 4][i] += (double)hb[w * 8 + i];
-            const double ntile = (double)nwg * 4 * ((N + 63) / 64);          // (wave, half-tile) pairs per wave group
-            static const char* nm[6] = {"dma-issue", "S0", "S1|exp0", "PV0|exp1", "PV1", "wait+barrier"};
-            for (int g = 0; g < 2; ++g) {
-                double tot = 0; for (int i = 0; i < 6; ++i) tot += sums[g][i];
-                fprintf(stderr, "[attn stamps] waves %d-%d: cycles per half-tile %.0f:", 4 * g, 4 * g + 3, tot / ntile);
-                for (int i = 0; i < 6; ++i) fprintf(stderr, "  %s %.0f (%.1f%%)", nm[i], sums[g][i] / ntile, 100.0 * sums[g][i] / tot);
-                fprintf(stderr, "\n");
-            }
-        }
+        p.stamps = stamp_buf(nwg, stream);
+#endif
+        hipLaunchKernelGGL((attn_fwd8p_kernel<128>), dim3((unsigned)nwg), dim3(512), FWD8_LDS, stream, p);
+#ifdef SCONF_ATTN_STAMP
+        { static const char* nm[6] = {"dma-issue", "S0", "S1|exp0", "PV0|exp1", "PV1", "wait+barrier"}; stamp_report("fwd8 (unit = 64-key half-tile)", p.stamps, nwg, (double)((N + 63) / 64), 6, nm, stream); }
 #endif
     } else if (D == 128) launch_fwd4<128>(p, grid, stream);
     else if (D == 256) launch_fwd4<256>(p, grid, stream);
@@ -1557,42 +1328,24 @@ SCONF_API int sconf_attn_bwd(const void* q, const void* k, const void* v, const 
     SCONF_REQUIRE((rot_cos == nullptr) == (rot_sin == nullptr), "sconf_attn_bwd: rot_cos and rot_sin go together");
     p.rot_cos = rot_cos; p.rot_sin = rot_sin;
     set_lds_attrs();
-    dim3 grid((unsigned)(cdiv(N, 128) * H * B)), block(256);
-    { const char* ex = getenv("SCONF_ATTN_XCD"); p.xcd_remap = !(ex && ex[0] == '0'); }       // A/B switch, read per call
+    const dim3 grid((unsigned)(cdiv(N, 128) * H * B));
     // dQ first: it computes delta = rowsum(dO * O) from fragments it holds anyway and writes it for the dK/dV kernel
-    if (D == 128) {
-        const char* eq = getenv("SCONF_ATTN_WIDE");
-        int64_t smax = 0;
-        for (int j = 0; j < 8; ++j) smax = std::max(smax, ss[j][1]);
-        const bool fits32 = (N - 1) * smax * 2 + 2 * D < (1L << 32);      // 8-wave kernels: 32-bit byte offsets inside a (batch, head) slice
-        if (!(eq && eq[0] == '0') && N >= 256 && fits32) {
-            static bool attr_set = false;
-            if (!attr_set) { (void)hipFuncSetAttribute((const void*)attn_bwd_dq8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256); attr_set = true; }
+    if (use_wide(D, N, all, 8)) {
+        const long nwg = cdiv(N, 256) * H * B;
 #ifdef SCONF_ATTN_STAMP
-            p.stamps = stamp_buf(cdiv(N, 256) * H * B, stream);
+        p.stamps = stamp_buf(nwg, stream);
 #endif
-            hipLaunchKernelGGL((attn_bwd_dq8_kernel<128>), dim3((unsigned)(cdiv(N, 256) * H * B)), dim3(512), 4 * 128 * 256, stream, p);
+        hipLaunchKernelGGL((attn_bwd_dq8_kernel<128>), dim3((unsigned)nwg), dim3(512), FWD8_LDS, stream, p);
 #ifdef SCONF_ATTN_STAMP
-            { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dQ chain", "wait+barrier"}; stamp_report("dq8 (unit = 32 keys)", p.stamps, cdiv(N, 256) * H * B, (double)((N + 31) / 32), 5, nm, stream); }
+        { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dQ chain", "wait+barrier"}; stamp_report("dq8 (unit = 32 keys)", p.stamps, nwg, (double)((N + 31) / 32), 5, nm, stream); }
+        p.stamps = stamp_buf(nwg, stream);
 #endif
-        } else
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), grid, block, fwd_lds<128>(), stream, p);
-        const char* e8 = getenv("SCONF_ATTN_DKDV8");           // "0" keeps the 4-wave dK/dV kernel (A/B, tests); read per call
-        const bool wide = !(e8 && e8[0] == '0');
-        if (wide && N >= 256 && fits32) {
-            static bool attr_set = false;
-            const int sh8 = 2 * (2 * 64 * 256 + 512) + 256 * 256;
-            if (!attr_set) { (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv8_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, sh8); attr_set = true; }
+        hipLaunchKernelGGL((attn_bwd_dkdv8_kernel<128>), dim3((unsigned)nwg), dim3(512), DKDV8_LDS, stream, p);
 #ifdef SCONF_ATTN_STAMP
-            p.stamps = stamp_buf(cdiv(N, 256) * H * B, stream);
+        { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dV|dK chains", "wait+barrier"}; stamp_report("dkdv8 (unit = 32 queries)", p.stamps, nwg, (double)((N + 31) / 32), 5, nm, stream); }
 #endif
-            hipLaunchKernelGGL((attn_bwd_dkdv8_kernel<128>), dim3((unsigned)(cdiv(N, 256) * H * B)), dim3(512), sh8, stream, p);
-#ifdef SCONF_ATTN_STAMP
-            { static const char* nm[5] = {"dma-issue", "S|dP chains", "exp*", "dV|dK chains", "wait+barrier"}; stamp_report("dkdv8 (unit = 32 queries)", p.stamps, cdiv(N, 256) * H * B, (double)((N + 31) / 32), 5, nm, stream); }
-#endif
-        } else
-            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<128>), grid, block, dkdv_lds<128>(), stream, p);
-    } else if (D == 256) launch_bwd4<256>(p, grid, stream);
+    } else if (D == 128) launch_bwd4<128>(p, grid, stream);
+    else if (D == 256) launch_bwd4<256>(p, grid, stream);
     else if (D == 64) launch_bwd4<64>(p, grid, stream);
     else launch_bwd4<32>(p, grid, stream);
     SCONF_LAUNCH_OK("sconf_attn_bwd");

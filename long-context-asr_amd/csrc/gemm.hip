@@ -22,11 +22,6 @@
 #include <algorithm>
 
 SCONF_API int sconf_num_cus(void);
-#ifdef SCONF_GEMM_PROBE
-static long long* g_probe_stamps = nullptr;
-// probe builds only: device buffer of 256 x 64 x 4 int64 that the 256x256 kernel fills with per-item time stamps (or null)
-SCONF_API int sconf_gemm_probe_stamps(void* buf) { g_probe_stamps = (long long*)buf; return 0; }
-#endif
 
 namespace {
 using namespace gemm_tile;
@@ -293,23 +288,16 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __re
     }
 }
 
-}  // namespace
-
-// C ABI -----------------------------------------------------------------------------------------
-// layout: 0 = NT (A[M][K], B[N][K]); 1 = NN (A[M][K], B[K][N]); 2 = TN (A[K][M], B[K][N]).
-namespace { struct RotSpec { const float* cos = nullptr; const float* sin = nullptr; int n = 0, cols = 0; }; thread_local RotSpec g_rot;
-            struct SmbSpec { const float* rowv = nullptr; float* colslab = nullptr; }; thread_local SmbSpec g_smb; }
-
-// Replaces: F.linear / fused_dense_cuda.linear_act_forward (fused_dense.py:277-279,329-332),
-// bias_act_linear_dgrad_bgrad (:354-356), linear_bias_wgrad (:113-115,338-340,375-378).
-SCONF_API int sconf_gemm_bf16(int layout, const void* A, const void* B, void* C,
-                              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
-                              const float* bias, const float* resid, int64_t ldr,
-                              const void* aux, int64_t ldaux, void* pre, int64_t ldpre,
-                              float alpha, int act, int out_f32, int split_k, hipStream_t stream) {
+// Argument checks and parameter fill shared by the GEMM entry points.  p arrives value-initialised, with the caller's fused-epilogue
+// inputs (rot_*, rowv / colslab) already set: SCONF_ACT_SMAXBWD passes only with rowv.  Returns 0 (p is complete), 1 (bad
+// arguments, error set) or -1 (an empty output, e.g. a batch with no rows: nothing to compute).
+int gemm_params(GemmParams& p, int layout, const void* A, const void* B, void* C,
+                int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                const float* bias, const float* resid, int64_t ldr, const void* aux, int64_t ldaux, void* pre, int64_t ldpre,
+                float alpha, int act, int out_f32, int split_k) {
     SCONF_REQUIRE(layout >= 0 && layout <= 2, "sconf_gemm_bf16: bad layout %d", layout);
     SCONF_REQUIRE(M >= 0 && N >= 0 && K > 0, "sconf_gemm_bf16: bad problem %ld x %ld x %ld (K must be positive)", (long)M, (long)N, (long)K);
-    if (M == 0 || N == 0) return 0;                    // an empty output (e.g. a batch with no rows): nothing to compute
+    if (M == 0 || N == 0) return -1;
     SCONF_REQUIRE(M < (1L << 31) && N < (1L << 31) && K < (1L << 31), "sconf_gemm_bf16: dims must be < 2^31");
     SCONF_REQUIRE(N % 4 == 0 && ldc % 4 == 0, "sconf_gemm_bf16: N and ldc must be multiples of 4 (N=%ld ldc=%ld)", (long)N, (long)ldc);
     if (layout == 0) SCONF_REQUIRE(N % 16 == 0 && ldc % 8 == 0, "sconf_gemm_bf16: the NT layout needs N %% 16 == 0 and ldc %% 8 == 0 (N=%ld ldc=%ld)", (long)N, (long)ldc);
@@ -325,56 +313,48 @@ SCONF_API int sconf_gemm_bf16(int layout, const void* A, const void* B, void* C,
     SCONF_REQUIRE(split_k == 1 || out_f32, "sconf_gemm_bf16: split-K writes f32 partial slabs and needs out_f32");
     if (act == SCONF_ACT_DGELU || act == SCONF_ACT_DSILU || act == SCONF_ACT_MULAUX) SCONF_REQUIRE(aux != nullptr, "sconf_gemm_bf16: aux epilogue needs aux");
     if (act == SCONF_ACT_GELU_DSAVE) SCONF_REQUIRE(pre != nullptr, "sconf_gemm_bf16: GELU_DSAVE needs the pre buffer");
-    SCONF_REQUIRE(act >= 0 && (act <= 6 || (act == SCONF_ACT_SMAXBWD && g_smb.rowv)), "sconf_gemm_bf16: bad act %d", act);
+    SCONF_REQUIRE(act >= 0 && (act <= 6 || (act == SCONF_ACT_SMAXBWD && p.rowv)), "sconf_gemm_bf16: bad act %d", act);
 
-    GemmParams p;
     p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C;
     p.M = (int)M; p.N = (int)N; p.K = (int)K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.bias = bias; p.resid = resid; p.ldr = ldr; p.aux = (const bf16*)aux; p.ldaux = ldaux;
     p.pre = (bf16*)pre; p.ldpre = ldpre; p.alpha = alpha; p.act = act; p.out_f32 = out_f32;
-#ifdef SCONF_GEMM_PROBE
-    { const char* d = getenv("SCONF_GEMM_DEBUG"); p.debug = d ? atoi(d) : 0; }
-    { const char* e = getenv("SCONF_GEMM_STAGGER"); p.stagger = e ? atoi(e) : 0; const char* f = getenv("SCONF_GEMM_STAGGER_MODE"); p.stagger_mode = f ? atoi(f) : 0; }
-    p.stamps = g_probe_stamps;
-#endif
-    { const char* e = getenv("SCONF_GEMM_GM"); p.gm = e ? atoi(e) : 0; }                  // tuning: L2 patch height of the 256-row kernels
-    p.rot_cos = g_rot.cos; p.rot_sin = g_rot.sin; p.rot_n = g_rot.n; p.rot_cols = g_rot.cols;   // set only inside sconf_gemm_qkv_rotary
-    p.rowv = g_smb.rowv; p.colslab = g_smb.colslab;                                              // set only inside sconf_gemm_softmax_bwd
     const int nkt = cdiv(K, BK);
     p.k_per_split = cdiv(nkt, split_k) * BK;
     const int splits = cdiv(K, p.k_per_split);
     p.splits = splits;
     p.split_stride = splits > 1 ? M * ldc : 0;
     if (splits > 1) SCONF_REQUIRE(!bias && !resid && act == SCONF_ACT_NONE && !pre, "sconf_gemm_bf16: split-K supports only the plain epilogue");
+    return 0;
+}
 
-    if (p.rot_cos || act == SCONF_ACT_SMAXBWD) {      // only the 256-row NT kernels have these epilogues: the caller falls back otherwise
-        if (getenv("SCONF_GEMM_NO_256") || !sconf_gemm256_eligible(p, layout)) return 2;
-        return sconf_gemm256_launch(p, layout, stream);
-    }
-    // A/B switch (read per call so that one process can compare both kernels): keep everything on the 128x128 kernel
+// Runs a complete parameter block: the 256-row kernels where they take the problem, the 128x128 kernel otherwise.  The rotary and
+// softmax-backward epilogues exist only in the 256-row NT kernels: without them the result is 2 and the caller falls back.
+int gemm_launch(const GemmParams& p, int layout, hipStream_t stream) {
+    // SCONF_GEMM_NO_256 keeps everything on the 128x128 kernel (read per call so that one process can compare both kernels)
     if (!getenv("SCONF_GEMM_NO_256") && sconf_gemm256_eligible(p, layout)) return sconf_gemm256_launch(p, layout, stream);
+    if (p.rot_cos || p.act == SCONF_ACT_SMAXBWD) return 2;
 
-    const int ntiles = cdiv(M, BM) * cdiv(N, BN);
-    dim3 grid(ntiles * splits), block(256);
+    const bool aks = layout == 2, bks = layout >= 1;
+    const int ntiles = cdiv(p.M, BM) * cdiv(p.N, BN);
+    dim3 grid(ntiles * p.splits), block(256);
     const size_t shmem = 4 * TILE_BYTES;
     static bool attr_set = false;
-    static bool no_glds = false;
     if (!attr_set) {
         const void* fns[6] = {(const void*)gemm_kernel<false, false, false>, (const void*)gemm_kernel<false, true, false>,
                               (const void*)gemm_kernel<true, true, false>, (const void*)gemm_kernel<false, false, true>,
                               (const void*)gemm_kernel<false, true, true>, (const void*)gemm_kernel<true, true, true>};
         for (int i = 0; i < 6; ++i) (void)hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        no_glds = getenv("SCONF_GEMM_NO_GLDS") != nullptr;      // A/B switch for benchmarking the two staging paths
         attr_set = true;
     }
     // LDS-DMA staging needs whole 64-deep K tiles (no zero fill), at least one full 8-row chunk to clamp to, and
-    // operands addressable with 32-bit byte offsets from a uniform base.
-    const bool glds = !no_glds && K % BK == 0 && M >= 8 && N >= 8 &&
-                      (long)(aks ? K : M) * lda * 2 < (1L << 32) && (long)(bks ? K : N) * ldb * 2 < (1L << 32);
+    // operands addressable with 32-bit byte offsets from a uniform base; register staging takes every other shape.
+    const bool glds = p.K % BK == 0 && p.M >= 8 && p.N >= 8 &&
+                      (long)(aks ? p.K : p.M) * p.lda * 2 < (1L << 32) && (long)(bks ? p.K : p.N) * p.ldb * 2 < (1L << 32);
     if (glds) {
         static int slots = 0;
         if (!slots) { int n = sconf_num_cus(); slots = 2 * (n > 0 ? n : 256); }
-        grid.x = std::min(ntiles * splits, slots);                // persistent: <= 2 resident workgroups per CU
+        grid.x = std::min(ntiles * p.splits, slots);              // persistent: <= 2 resident workgroups per CU
         if (layout == 0)      hipLaunchKernelGGL((gemm_kernel<false, false, true>), grid, block, shmem, stream, p);
         else if (layout == 1) hipLaunchKernelGGL((gemm_kernel<false, true, true>), grid, block, shmem, stream, p);
         else                  hipLaunchKernelGGL((gemm_kernel<true, true, true>), grid, block, shmem, stream, p);
@@ -385,6 +365,24 @@ SCONF_API int sconf_gemm_bf16(int layout, const void* A, const void* B, void* C,
     }
     SCONF_LAUNCH_OK("sconf_gemm_bf16");
     return 0;
+}
+
+}  // namespace
+
+// C ABI -----------------------------------------------------------------------------------------
+// layout: 0 = NT (A[M][K], B[N][K]); 1 = NN (A[M][K], B[K][N]); 2 = TN (A[K][M], B[K][N]).
+
+// Replaces: F.linear / fused_dense_cuda.linear_act_forward (fused_dense.py:277-279,329-332),
+// bias_act_linear_dgrad_bgrad (:354-356), linear_bias_wgrad (:113-115,338-340,375-378).
+SCONF_API int sconf_gemm_bf16(int layout, const void* A, const void* B, void* C,
+                              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                              const float* bias, const float* resid, int64_t ldr,
+                              const void* aux, int64_t ldaux, void* pre, int64_t ldpre,
+                              float alpha, int act, int out_f32, int split_k, hipStream_t stream) {
+    GemmParams p{};
+    if (const int rc = gemm_params(p, layout, A, B, C, M, N, K, lda, ldb, ldc, bias, resid, ldr, aux, ldaux, pre, ldpre, alpha, act, out_f32, split_k))
+        return rc < 0 ? 0 : rc;
+    return gemm_launch(p, layout, stream);
 }
 
 SCONF_API int sconf_rotary_inplace(void* qkv, const float* cos_tab, const float* sin_tab, int64_t B, int64_t N, int64_t H, int64_t D, hipStream_t stream);
@@ -398,14 +396,15 @@ SCONF_API int sconf_gemm_qkv_rotary(const void* A, const void* W, void* C, int64
                                     int64_t seq_len, hipStream_t stream) {
     SCONF_REQUIRE(cos_tab && sin_tab && seq_len > 0 && M % seq_len == 0, "sconf_gemm_qkv_rotary: tables / seq_len (M=%ld seq_len=%ld)", (long)M, (long)seq_len);
     const int64_t N = 3 * H * D;
-    int rc = 2;
     if (D == 128 && !getenv("SCONF_QKV_ROT_EPILOGUE_OFF")) {
-        g_rot.cos = cos_tab; g_rot.sin = sin_tab; g_rot.n = (int)seq_len; g_rot.cols = (int)(2 * H * D);
-        rc = sconf_gemm_bf16(0, A, W, C, M, N, K, lda, ldb, N, bias, nullptr, 0, nullptr, 0, nullptr, 0, 1.f, SCONF_ACT_NONE, 0, 1, stream);
-        g_rot = RotSpec();
+        GemmParams p{};
+        p.rot_cos = cos_tab; p.rot_sin = sin_tab; p.rot_n = (int)seq_len; p.rot_cols = (int)(2 * H * D);
+        if (const int rc = gemm_params(p, 0, A, W, C, M, N, K, lda, ldb, N, bias, nullptr, 0, nullptr, 0, nullptr, 0, 1.f, SCONF_ACT_NONE, 0, 1))
+            return rc < 0 ? 0 : rc;
+        const int rc = gemm_launch(p, 0, stream);
+        if (rc != 2) return rc;
     }
-    if (rc != 2) return rc;
-    rc = sconf_gemm_bf16(0, A, W, C, M, N, K, lda, ldb, N, bias, nullptr, 0, nullptr, 0, nullptr, 0, 1.f, SCONF_ACT_NONE, 0, 1, stream);
+    const int rc = sconf_gemm_bf16(0, A, W, C, M, N, K, lda, ldb, N, bias, nullptr, 0, nullptr, 0, nullptr, 0, 1.f, SCONF_ACT_NONE, 0, 1, stream);
     if (rc) return rc;
     return sconf_rotary_inplace(C, cos_tab, sin_tab, M / seq_len, seq_len, H, D, stream);
 }
@@ -419,15 +418,16 @@ SCONF_API int sconf_gemm_qkv_rotary(const void* A, const void* W, void* C, int64
 SCONF_API int sconf_gemm_softmax_bwd(const void* dy, const void* Wt, const void* probs, const float* delta, void* dl, float* colslab,
                                      int64_t M, int64_t V, int64_t K, int64_t lddy, int64_t ldw, int64_t ldp, hipStream_t stream) {
     SCONF_REQUIRE(delta && colslab && probs, "sconf_gemm_softmax_bwd: delta, colslab and probs are required");
-    g_smb.rowv = delta; g_smb.colslab = colslab;
-    const int rc = sconf_gemm_bf16(0, dy, Wt, dl, M, V, K, lddy, ldw, V, nullptr, nullptr, 0, probs, ldp, nullptr, 0, 1.f, SCONF_ACT_SMAXBWD, 0, 1, stream);
-    g_smb = SmbSpec();
-    return rc;
+    GemmParams p{};
+    p.rowv = delta; p.colslab = colslab;
+    if (const int rc = gemm_params(p, 0, dy, Wt, dl, M, V, K, lddy, ldw, V, nullptr, nullptr, 0, probs, ldp, nullptr, 0, 1.f, SCONF_ACT_SMAXBWD, 0, 1))
+        return rc < 0 ? 0 : rc;
+    return gemm_launch(p, 0, stream);
 }
 
 // Which kernel sconf_gemm_bf16 runs for a problem (diagnostics / benchmark bookkeeping; same decision code as the launch):
-// 0 = gemm_kernel (128x128 tile, 4 waves), 1 = gemm256_kernel<NT, 256 wide>, 2 = gemm256_kernel<NT, 192 wide>,
-// 3 = gemm256_kernel<TN>.  (2 is gemm192_kernel unless SCONF_GEMM_192_4PHASE asks for the 4-phase template.)
+// 0 = gemm_kernel (128x128 tile, 4 waves), 1 = gemm256_kernel<NT> (256 wide), 2 = gemm192_kernel (NT, 192 wide),
+// 3 = gemm256_kernel<TN>.
 SCONF_API int sconf_gemm_variant(int layout, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int split_k, int act,
                                  int has_resid, int has_pre) {
     if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || K <= 0 || split_k < 1) return -1;

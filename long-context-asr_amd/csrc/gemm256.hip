@@ -35,8 +35,8 @@ SCONF_API int sconf_num_cus(void);
 namespace {
 using namespace gemm_tile;
 
-// Tile = 256 rows x (128 + 64 * JH) columns: JH = 2 -> 256x256; JH = 1 -> 256x192 (NT only), which turns the 384 tiles of
-// an N = 768 projection (1.5 rounds over 256 CUs) into 512 (exactly 2 rounds).
+// Tile = 256 rows x (128 + 64 * JH) columns: JH = 2 -> 256x256 (gemm256_kernel); JH = 1 -> 256x192 (gemm192_kernel, NT only),
+// which turns the 384 tiles of an N = 768 projection (1.5 rounds over 256 CUs) into 512 (exactly 2 rounds).
 constexpr int TM = 256, TK = 64;
 constexpr int HT = 128 * 64 * 2;                   // one half-tile image, 16 KiB (B1 of the 192-wide tile uses half of it)
 constexpr int BUF = 4 * HT;                        // A0 | A1 | B0 | B1
@@ -465,28 +465,20 @@ template <int JH> __device__ __forceinline__ void wait_window(bool streaming) {
     else VMCNT(7);
 }
 
-template <bool KS, int JH, int EK = -1>
+template <bool KS, int EK = -1>
 __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
-    constexpr int WC = 32 + 16 * JH, TN = 4 * WC;
+    constexpr int JH = 2, TN = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][A0 | A1 | B0 | B1], 128 KiB: the ONLY LDS object
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     Sched sc;
-    sc.tn = TN; sc.tiles_n = p.N / TN; sc.tiles_m = p.M / TM; sc.ntiles = sc.tiles_m * sc.tiles_n; sc.total = sc.ntiles * p.splits; sc.gm = p.gm > 0 ? p.gm : (sc.tiles_n >= 8 ? 2 * GM2 : GM2);
+    sc.tn = TN; sc.tiles_n = p.N / TN; sc.tiles_m = p.M / TM; sc.ntiles = sc.tiles_m * sc.tiles_n; sc.total = sc.ntiles * p.splits; sc.gm = sc.tiles_n >= 8 ? 2 * GM2 : GM2;
     if ((int)blockIdx.x >= sc.total) return;
-#ifdef SCONF_GEMM_PROBE
-    if (p.stagger > 0) {
-        const int b = blockIdx.x;
-        const int ph = p.stagger_mode == 0 ? (b & 7) : p.stagger_mode == 1 ? ((b >> 3) & 7) : ((b + (b >> 3)) & 7);
-        for (int i = 0; i < ph * p.stagger; ++i) __builtin_amdgcn_s_sleep(16);
-    }
-    int probe_item = 0;
-#endif
 
     const int ekind = __builtin_amdgcn_readfirstlane(epilogue_kind(p));
     DmaOffs<KS, false, JH> oa; DmaOffs<KS, true, JH> ob;
-    oa.set(p.lda, tid); ob.set(p.ldb, tid, !KS && JH == 2 && p.rot_cos != nullptr);
+    oa.set(p.lda, tid); ob.set(p.ldb, tid, !KS && p.rot_cos != nullptr);
     auto issue_a = [&](const Cursor& c, int h) {
         if (!c.valid) return;
         const long k0 = c.it.kbeg + c.kt * TK;
@@ -517,7 +509,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     pc.advance(p, sc);
     issue_a(pc, 0); issue_b(pc, 0);
     if (pc.valid) wait_window<JH>(true);             // A0, B0 of K-tile 0 have landed
-    else if (JH == 2) VMCNT(4); else VMCNT(3);
+    else VMCNT(4);
     __builtin_amdgcn_s_barrier();
 
     int cur = 0;
@@ -580,7 +572,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                 if constexpr (KS) frag_pair_ks(buf + 3 * HT, 32 * wc + 16 * j + 4 * (lane & 3), lane, bhi[j][0], bhi[j][1]);
                 else {
 #pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) bhi[j][kk] = frag_b<KS, JH == 1>(buf + 3 * HT, wc, j, kk, lane);
+                    for (int kk = 0; kk < 2; ++kk) bhi[j][kk] = frag_b<KS, false>(buf + 3 * HT, wc, j, kk, lane);
                 }
             }
             GSTAMP(6);
@@ -668,26 +660,15 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
             cur ^= 1;
         }
         // ---- epilogue: both wave rows concurrently; one specialised, contiguous code path per (activation, residual) ------
-#ifdef SCONF_GEMM_PROBE
-        long long* st = (p.stamps && tid == 0 && probe_item < 64) ? p.stamps + ((long)blockIdx.x * 64 + probe_item) * 4 : nullptr;
-        if (st) { st[0] = __builtin_amdgcn_s_memrealtime(); st[1] = __builtin_amdgcn_s_memtime(); }
-        if (p.debug != 2 || acc[0][0][0][0] == 1.2345e-30f)
-#endif
-        {
-            if constexpr (KS) epilogue256<SCONF_ACT_NONE, false, true, JH>(p, acc, cit, wr, wc, lane);
-            else if constexpr (EK >= 0) EPILOGUE_ONE(EK, JH);
-            else EPILOGUE_NT(JH);
-        }
+        if constexpr (KS) epilogue256<SCONF_ACT_NONE, false, true, JH>(p, acc, cit, wr, wc, lane);
+        else if constexpr (EK >= 0) EPILOGUE_ONE(EK, JH);
+        else EPILOGUE_NT(JH);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 2 + JH; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef SCONF_GEMM_PROBE
-        if (st) { st[2] = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st[3] = __builtin_amdgcn_s_memtime(); }
-        ++probe_item;
-#endif
         GSTAMP(4);                                    // epilogue (+ accumulator clears)
         __builtin_amdgcn_s_barrier();                 // re-align the two wave rows
         GSTAMP(5);
@@ -700,9 +681,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 }
 
 // ---- 256x192 tile, NT, THREE phases per K-tile -------------------------------------------------------------------------
-// The 4-phase schedule above on a 192-wide tile has MFMA clusters of 16 / 8 / 8 / 16 (the hi column half is one 16-wide
-// tile per wave), so in the two short phases the other wave row's load section outlasts the MFMAs.  With both A quadrants
-// resident (32 more VGPRs; the 192-wide tile has 32 fewer accumulators) the K-tile folds into three 16-MFMA phases:
+// The 4-phase schedule above on a 192-wide tile (retired, DESIGN) had MFMA clusters of 16 / 8 / 8 / 16 (the hi column half is
+// one 16-wide tile per wave), so in the two short phases the other wave row's load section outlasted the MFMAs.  With both A
+// quadrants resident (32 more VGPRs; the 192-wide tile has 32 fewer accumulators) the K-tile folds into three 16-MFMA phases:
 //   P0  read B-lo, A-lo     issue A1, B1 of K-tile s+1    MFMA  A-lo x B-lo
 //   P1  read B-hi, A-hi     -                             MFMA  A-lo x B-hi, A-hi x B-hi
 //   P2  -                   issue A0, B0 of K-tile s+2    MFMA  A-hi x B-lo
@@ -718,7 +699,7 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     Sched sc;
-    sc.tn = TN; sc.tiles_n = p.N / TN; sc.tiles_m = p.M / TM; sc.ntiles = sc.tiles_m * sc.tiles_n; sc.total = sc.ntiles * p.splits; sc.gm = p.gm > 0 ? p.gm : (sc.tiles_n >= 8 ? 2 * GM2 : GM2);
+    sc.tn = TN; sc.tiles_n = p.N / TN; sc.tiles_m = p.M / TM; sc.ntiles = sc.tiles_m * sc.tiles_n; sc.total = sc.ntiles * p.splits; sc.gm = sc.tiles_n >= 8 ? 2 * GM2 : GM2;
     if ((int)blockIdx.x >= sc.total) return;
 
     const int ekind = __builtin_amdgcn_readfirstlane(epilogue_kind(p));
@@ -819,13 +800,8 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
             if (!(wr && last)) __builtin_amdgcn_s_barrier();   // the lagging row goes straight into its epilogue
             cur ^= 1;
         }
-#ifdef SCONF_GEMM_PROBE
-        if (p.debug != 2 || acc[0][0][0][0] == 1.2345e-30f)
-#endif
-        {
-            if constexpr (EK >= 0) EPILOGUE_ONE(EK, JH);
-            else EPILOGUE_NT(JH);
-        }
+        if constexpr (EK >= 0) EPILOGUE_ONE(EK, JH);
+        else EPILOGUE_NT(JH);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -846,10 +822,6 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
 static int pick_width(const GemmParams& p, int layout, int cus) {
     if (p.M % TM || p.K % TK || p.k_per_split % TK) return 0;                 // whole tiles only: the kernels floor M / TM and K / TK
     if (p.rot_cos) return (layout == 0 && p.N % 256 == 0) ? 256 : 0;          // the rotary epilogue exists for the 256-wide tile
-    if (const char* e = getenv("SCONF_GEMM_256_WIDTH")) {                 // benchmarking override
-        const int w = atoi(e);
-        return ((w == 256 || (w == 192 && layout == 0)) && p.N % w == 0) ? w : 0;
-    }
     long best = 0; int bw = 0;
     for (int w : {256, 192}) {
         if (p.N % w || (w == 192 && layout != 0)) continue;
@@ -887,11 +859,11 @@ int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
     static bool attr_set = false;
     const size_t shmem = 2 * BUF;
     if (!attr_set) {
-        const void* fns[] = {(const void*)gemm256_kernel<false, 2>, (const void*)gemm256_kernel<false, 1>, (const void*)gemm256_kernel<true, 2>,
-                             (const void*)gemm256_kernel<false, 2, 0>, (const void*)gemm256_kernel<false, 2, 1>, (const void*)gemm256_kernel<false, 2, 2>,
-                             (const void*)gemm256_kernel<false, 2, 3>, (const void*)gemm256_kernel<false, 2, 4>, (const void*)gemm256_kernel<false, 2, 5>,
-                             (const void*)gemm256_kernel<false, 2, 7>, (const void*)gemm256_kernel<false, 2, 8>, (const void*)gemm256_kernel<false, 2, 9>,
-                             (const void*)gemm256_kernel<false, 2, 10>, (const void*)gemm256_kernel<false, 2, 11>, (const void*)gemm256_kernel<false, 2, 12>,
+        const void* fns[] = {(const void*)gemm256_kernel<false>, (const void*)gemm256_kernel<true>,
+                             (const void*)gemm256_kernel<false, 0>, (const void*)gemm256_kernel<false, 1>, (const void*)gemm256_kernel<false, 2>,
+                             (const void*)gemm256_kernel<false, 3>, (const void*)gemm256_kernel<false, 4>, (const void*)gemm256_kernel<false, 5>,
+                             (const void*)gemm256_kernel<false, 7>, (const void*)gemm256_kernel<false, 8>, (const void*)gemm256_kernel<false, 9>,
+                             (const void*)gemm256_kernel<false, 10>, (const void*)gemm256_kernel<false, 11>, (const void*)gemm256_kernel<false, 12>,
                              (const void*)gemm192_kernel<11>, (const void*)gemm192_kernel<12>, (const void*)gemm192_kernel<-1>, (const void*)gemm192_kernel<0>,
                              (const void*)gemm192_kernel<1>, (const void*)gemm192_kernel<2>, (const void*)gemm192_kernel<3>, (const void*)gemm192_kernel<4>,
                              (const void*)gemm192_kernel<5>, (const void*)gemm192_kernel<9>};
@@ -902,14 +874,11 @@ int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
     const int w = pick_width(p, layout, cus);
     const int total = (p.M / TM) * (p.N / w) * p.splits;
     dim3 grid(std::min(total, cus)), block(512);
-    // NT: one kernel instantiation per specialised epilogue kind (SCONF_GEMM_ONE_KERNEL: the kernel that switches, A/B; kinds 9 / 10
-    // exist only as instantiations)
-    int ek = layout == 2 ? -1 : epilogue_kind(p);
-    if (ek == 6 || (ek < 9 && getenv("SCONF_GEMM_ONE_KERNEL"))) ek = -1;
-    if (ek >= 11 && getenv("SCONF_GEMM_ONE_KERNEL")) ek = -1;
-#define L256(EK_) hipLaunchKernelGGL((gemm256_kernel<false, 2, EK_>), grid, block, shmem, stream, p)
+    // NT: one kernel instantiation per specialised epilogue kind; the kernel that switches (EK = -1) takes kind 6
+    const int ek = layout == 2 ? -1 : epilogue_kind(p);
+#define L256(EK_) hipLaunchKernelGGL((gemm256_kernel<false, EK_>), grid, block, shmem, stream, p)
 #define L192(EK_) hipLaunchKernelGGL(gemm192_kernel<EK_>, grid, block, shmem, stream, p)
-    if (layout == 2)   hipLaunchKernelGGL((gemm256_kernel<true, 2>), grid, block, shmem, stream, p);
+    if (layout == 2)   hipLaunchKernelGGL((gemm256_kernel<true>), grid, block, shmem, stream, p);
     else if (w == 256) {
         switch (ek) {
             case 0: L256(0); break; case 1: L256(1); break; case 2: L256(2); break; case 3: L256(3); break; case 4: L256(4); break;
@@ -917,8 +886,7 @@ int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
             case 11: L256(11); break; case 12: L256(12); break;
             default: L256(-1);
         }
-    } else if (getenv("SCONF_GEMM_192_4PHASE")) hipLaunchKernelGGL((gemm256_kernel<false, 1>), grid, block, shmem, stream, p);   // A/B
-    else {
+    } else {
         switch (ek) {
             case 0: L192(0); break; case 1: L192(1); break; case 2: L192(2); break; case 3: L192(3); break; case 4: L192(4); break;
             case 5: L192(5); break; case 9: L192(9); break; case 11: L192(11); break; case 12: L192(12); break;

@@ -19,18 +19,12 @@ struct GemmParams {
     long split_stride;                              // split-K: partial-sum slab s lives at C + s * split_stride (f32)
     int k_per_split;                                // multiple of BK
     int splits;
-    int gm;                                         // row panels per L2 patch of the 256-row kernels (0 = default)
     // NeoX rotary fused into the epilogue of the qkv projection (sconf_gemm_qkv_rotary; 256x256 NT kernel, head_dim 128): output
     // columns < rot_cols are (head, d) with d < 128; row r is position r % rot_n; tables (rot_n, 64) f32.  null = no rotation.
     const float* rot_cos; const float* rot_sin; int rot_n, rot_cols;
     // softmax backward in the epilogue (sconf_gemm_softmax_bwd; 256-row NT kernel): out = (acc - rowv[m]) * aux[m][n], and the column
     // sums of the output of every (256-row item, wave row) go to colslab[2 * m0 / 256 + wave row][N] (f32; the bias gradient).
     const float* rowv; float* colslab;
-#ifdef SCONF_GEMM_PROBE
-    int debug;                                      // probe builds only (make PROBE=1; SCONF_GEMM_DEBUG): 1 = skip epilogue stores, 2 = skip the epilogue
-    long long* stamps;                              // probe: per workgroup [64 items][4] {realtime at epilogue start, cycles at start, at end, after the next item's first wait}
-    int stagger, stagger_mode;                      // probe: start-up phase offsets between workgroups (units of 1024 cycles)
-#endif
 };
 
 __device__ __forceinline__ int swz_strided(int k) { return ((k & 3) << 1) | (((k >> 3) & 1) << 3); }
@@ -79,17 +73,12 @@ __device__ __forceinline__ void epi_math_store_at(const GemmParams& p, float (&v
 #pragma unroll
         for (int e = 0; e < W; ++e) v[e] += bs[e];
     }
-#ifdef SCONF_GEMM_PROBE
-    const bool st = p.debug != 1 || v[0] == 1.2345e-30f;
-#else
-    constexpr bool st = true;
-#endif
     if (act == SCONF_ACT_GELU_DSAVE) {
         float dg[W];
 #pragma unroll
         for (int e = 0; e < W; ++e) gelu_both(v[e], v[e], dg[e]);
-        if (st) storev<W>(p.pre + poff, dg);
-    } else if (has_pre) { if (st) storev<W>(p.pre + poff, v); }
+        storev<W>(p.pre + poff, dg);
+    } else if (has_pre) storev<W>(p.pre + poff, v);
     if (act == SCONF_ACT_MULAUX) {
 #pragma unroll
         for (int e = 0; e < W; ++e) v[e] *= ax[e];
@@ -113,16 +102,12 @@ __device__ __forceinline__ void epi_math_store_at(const GemmParams& p, float (&v
 #pragma unroll
         for (int e = 0; e < W; ++e) v[e] = v[e] * p.alpha + rs[e];
     }
-    if (!st) return;
     if (f32o) storev<W>(reinterpret_cast<float*>(p.C) + split * p.split_stride + coff, v);
     else      storev<W>(reinterpret_cast<bf16*>(p.C) + coff, v);
 }
 // Store-only step of a two-phase epilogue: v already holds resid + alpha * act(acc + bias).
 template <int W, int FL>
 __device__ __forceinline__ void epi_store_at(const GemmParams& p, const float (&v)[W], long coff, int split) {
-#ifdef SCONF_GEMM_PROBE
-    if (p.debug == 1 && v[0] != 1.2345e-30f) return;
-#endif
     if ((FL & 2) != 0) storev<W>(reinterpret_cast<float*>(p.C) + split * p.split_stride + coff, v);
     else               storev<W>(reinterpret_cast<bf16*>(p.C) + coff, v);
 }

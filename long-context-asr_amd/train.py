@@ -8,7 +8,6 @@ schedule `backprop_every: 1`), on synthetic mel batches, with optional single-no
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
@@ -37,7 +36,7 @@ class Trainer:
         """fused_loss: run the decoder head and the CTC loss as one operator (model(..., ctc_targets=...)); False keeps the
         reference's two calls (posteriors, then CTCLoss) - same loss and gradients, 25 GB more HBM traffic per step at B = 128."""
         self.model = model
-        self.fused_loss = fused_loss and os.environ.get('SCONF_FUSED_LOSS', '1') != '0'       # env switch: A/B runs
+        self.fused_loss = fused_loss
         self.opt = MADGRAD(model.parameters(), lr=lr)
         self.ctc = CTCLoss(blank=model.decoder.num_classes - 1, reduction='sum')
         self.clip_value = clip_value
