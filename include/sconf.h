@@ -232,6 +232,27 @@ int sconf_overlap_finalize(const float* acc, const float* count, float* out, int
 /* idx[m] = argmax_c x[m][c], first index on ties: GreedyCTCDecoder.forward (lcasr/decoding/greedy.py:19). */
 int sconf_argmax_rows(const float* x, int64_t M, int64_t C, int32_t* idx, sconf_stream_t stream);
 
+/* ---- SpecAugment and dynamic evaluation (lcasr/utils/augmentation.py:10-100, lcasr/eval/dynamic_eval.py:11-142) -----------
+ * sconf_spec_mask: dst (B,F,T) f32 = src (batch stride src_batch_stride elements; 0 broadcasts one spectrogram to every row of
+ * the batch) with *mask_value (a DEVICE f32: no host sync between the mean and the masking) wherever t lies in one of row b's
+ * n_t time intervals t_iv (B,n_t,2) or f in one of its n_f frequency intervals f_iv (B,n_f,2); int32, half-open [start, end),
+ * an empty interval masks nothing.  All masks fill the same value, so the union equals the reference's sequence of masked_fills
+ * (augmentation.py:83-98, torchaudio mask_along_axis[_iid]); with stride 0 it also replaces repeat + clone (dynamic_eval.py:84-86). */
+int sconf_spec_mask(const float* src, int64_t src_batch_stride, float* dst, int64_t B, int64_t F, int64_t T, const int32_t* t_iv,
+                    int64_t n_t, const int32_t* f_iv, int64_t n_f, const float* mask_value, sconf_stream_t stream);
+/* *out (device f32) = mean of x (B,R,T) f32 contiguous; with lengths (B) int32 only over t < lengths[b] (specgram.mean() and its
+ * length-masked form, augmentation.py:73).  Fixed summation order; workspace of sconf_mean_f32_workspace(B*R*T) bytes. */
+int64_t sconf_mean_f32_workspace(int64_t n);
+int sconf_mean_f32(const float* x, int64_t B, int64_t R, int64_t T, const int32_t* lengths, float* out, void* workspace,
+                   int64_t workspace_bytes, sconf_stream_t stream);
+/* Greedy CTC labels on the device: per sequence of x (B,N,C) f32 the frame arg-maxes (first index on ties, as sconf_argmax_rows),
+ * repeats merged, blanks dropped, frames >= lengths[b] (int32, may be NULL) ignored -> targets (B,S_cap) int32 in order, zero
+ * padded, target_lengths (B) int32, -1 where a sequence has more than S_cap labels (nothing is written past the buffer).
+ * idx (B*N) int32 receives the frame arg-maxes.  GreedyCTCDecoder.forward (lcasr/decoding/greedy.py:19-21) followed by the
+ * re-encoding of dynamic_eval.py:92-93, without moving the posteriors or the index vector to the host. */
+int sconf_ctc_collapse(const float* x, int64_t B, int64_t N, int64_t C, const int32_t* lengths, int32_t blank, int32_t* idx,
+                       int32_t* targets, int64_t S_cap, int32_t* target_lengths, sconf_stream_t stream);
+
 /* Fused MADGRAD + global-norm clip over flat f32 buffers (lcasr/optim/madgrad.py:81-212, exp/train.py:46-61). */
 /* *out += sum(g^2), per-workgroup sums added in a fixed order: workspace of sconf_sumsq_workspace(n) bytes */
 int64_t sconf_sumsq_workspace(int64_t n);

@@ -670,3 +670,59 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     idx = torch.empty(M, dtype=torch.int32, device=x.device)
     _lib.call('sconf_argmax_rows', _p(x), M, Cc, _p(idx), _stream())
     return idx
+
+
+# ------------------------------------------------------------------------------------------------
+# SpecAugment and dynamic evaluation (plain-PyTorch references: tests/dyneval_refs.py)
+# ------------------------------------------------------------------------------------------------
+def spec_mask(src: torch.Tensor, t_iv: torch.Tensor, f_iv: torch.Tensor, mask_value: torch.Tensor, batch: Optional[int] = None) -> torch.Tensor:
+    """src (Bs,F,T) f32 -> (B,F,T) with *mask_value (a device f32 scalar tensor) wherever t is in one of row b's intervals
+    t_iv (B,n_t,2) or f in one of f_iv (B,n_f,2) (int32, half-open).  Bs == B, or Bs == 1 broadcast to `batch` = B rows."""
+    _chk(src, 'src', torch.float32); _chk(t_iv, 't_iv', torch.int32); _chk(f_iv, 'f_iv', torch.int32)
+    _chk(mask_value, 'mask_value', torch.float32)
+    if src.dim() != 3: raise ValueError(f'src must be (batch, freq, time), got {tuple(src.shape)}')
+    Bs, Fq, T = src.shape
+    B = Bs if batch is None else int(batch)
+    if B != Bs and Bs != 1: raise ValueError(f'src batch {Bs} can only be broadcast to {B} rows when it is 1')
+    if t_iv.dim() != 3 or f_iv.dim() != 3 or t_iv.shape[0] != B or f_iv.shape[0] != B or t_iv.shape[2] != 2 or f_iv.shape[2] != 2:
+        raise ValueError(f't_iv / f_iv must be ({B}, n, 2), got {tuple(t_iv.shape)} / {tuple(f_iv.shape)}')
+    if mask_value.numel() != 1: raise ValueError('mask_value must hold one element')
+    dst = torch.empty(B, Fq, T, dtype=torch.float32, device=src.device)
+    _lib.call('sconf_spec_mask', _p(src), 0 if B != Bs else Fq * T, _p(dst), B, Fq, T, _p(t_iv), t_iv.shape[1], _p(f_iv), f_iv.shape[1],
+              _p(mask_value), _stream())
+    return dst
+
+
+def mean_f32(x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mean of an f32 tensor as a device scalar (shape ()), same bits on every call; with lengths (B,) int32 and x (B,...,T) only
+    over t < lengths[b]."""
+    _chk(x, 'x', torch.float32)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    if lengths is None:
+        B, R, T = 1, 1, x.numel()
+    else:
+        _chk(lengths, 'lengths', torch.int32)
+        if x.dim() < 2 or lengths.shape != (x.shape[0],): raise ValueError('lengths must be (batch,) for x (batch, ..., time)')
+        B, T = x.shape[0], x.shape[-1]
+        R = x.numel() // max(B * T, 1)
+    nws = int(_lib.load().sconf_mean_f32_workspace(x.numel()))
+    ws = _workspace(nws, x.device)
+    _lib.call('sconf_mean_f32', _p(x), B, R, T, _p(lengths), _p(out), _p(ws), nws, _stream())
+    return out
+
+
+def ctc_collapse(x: torch.Tensor, lengths: Optional[torch.Tensor], blank: int, s_cap: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy CTC labels of x (B,N,C) f32 on the device: targets (B,s_cap) int32 (zero padded; s_cap defaults to N, which always
+    suffices) and target_lengths (B,) int32 (-1: more than s_cap labels)."""
+    _chk(x, 'x', torch.float32)
+    if x.dim() != 3: raise ValueError(f'x must be (batch, frames, classes), got {tuple(x.shape)}')
+    B, N, Cc = x.shape
+    if lengths is not None:
+        _chk(lengths, 'lengths', torch.int32)
+        if lengths.shape != (B,): raise ValueError('lengths must be (batch,)')
+    s_cap = N if s_cap is None else int(s_cap)
+    idx = torch.empty(B * N, dtype=torch.int32, device=x.device)
+    targets = torch.empty(B, s_cap, dtype=torch.int32, device=x.device)
+    tl = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.call('sconf_ctc_collapse', _p(x), B, N, Cc, _p(lengths), int(blank), _p(idx), _p(targets), s_cap, _p(tl), _stream())
+    return targets, tl

@@ -32,10 +32,14 @@ def synthetic_batch(B: int, T: int, vocab_size: int, seed: int = 0, device='cuda
 
 class Trainer:
     def __init__(self, model, lr: float = 3e-3, clip_value: float = 0.8, global_batch: Optional[int] = None,
-                 bucket_bytes: int = 64 << 20, fused_loss: bool = True):
+                 bucket_bytes: int = 64 << 20, fused_loss: bool = True, spec_augment=None):
         """fused_loss: run the decoder head and the CTC loss as one operator (model(..., ctc_targets=...)); False keeps the
-        reference's two calls (posteriors, then CTCLoss) - same loss and gradients, 25 GB more HBM traffic per step at B = 128."""
+        reference's two calls (posteriors, then CTCLoss) - same loss and gradients, 25 GB more HBM traffic per step at B = 128.
+        spec_augment: optional module applied as spec_augment(audio, lengths) to every batch before the forward
+        (utils.augmentation.SpecAugment; exp/train.py:64-68,227).  The epoch / warm-up gate stays with the caller, who passes or
+        withholds the module; None = no augmentation."""
         self.model = model
+        self.spec_augment = spec_augment
         self.fused_loss = fused_loss
         self.opt = MADGRAD(model.parameters(), lr=lr)
         self.ctc = CTCLoss(blank=model.decoder.num_classes - 1, reduction='sum')
@@ -49,6 +53,8 @@ class Trainer:
         The loss is scaled by 100 / (norm_frames * norm_batch): the reference divides by the CONSTANT chunk_size * batch_size
         (exp/train.py:275), so ragged last chunks and shrunken batches weigh less; defaults: this batch's width / batch."""
         B, _, T = audio.shape
+        if self.spec_augment is not None:
+            audio = self.spec_augment(audio, lengths)
         if self.fused_loss:                              # head + log_softmax + CTC as one operator: the posteriors are never written
             loss = self.model(audio, length=lengths, ctc_targets=(targets, target_lengths))['ctc_nll'].sum()
         else:
