@@ -140,6 +140,10 @@ int sconf_mask_rows(void* x, int dtype, const int32_t* lengths, int64_t B, int64
  * strides {batch, token, head}; lengths: int32 [B] or NULL; window (-1 = unbounded); lse: f32 (B,H,N).
  * sconf_attn_bwd: delta is f32 scratch of 2*B*H*N floats (the dQ kernel, which runs first, leaves the row statistics of the
  * dK/dV kernel there: -rowsum(dO*O) and -lse*log2(e)). */
+/* Which kernel set the two calls below run (bookkeeping for tests and benchmarks, in the manner of sconf_gemm_variant): 8 = the
+ * 8-wave kernels (head_dim 128, N >= 256, views addressable with 32-bit byte offsets), 4 = the 4-wave ones, -1 = unsupported head_dim.
+ * token_stride: the largest token stride (elements) among the views passed. */
+int sconf_attn_waves(int64_t D, int64_t N, int64_t token_stride);
 int sconf_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* lengths,
                    int64_t B, int64_t N, int64_t H, int64_t D, const int64_t* q_strides /*host*/, const int64_t* k_strides /*host*/,
                    const int64_t* v_strides /*host*/, const int64_t* o_strides /*host*/, int win_left, int win_right,
@@ -163,6 +167,11 @@ int sconf_brn_finalize(const double* stats, int64_t count, float* running_mean, 
                        int64_t* num_batches_tracked, const float* weight, const float* bias, float* coef, int64_t d,
                        int training, float eps, float momentum, sconf_stream_t stream);
 int sconf_affine_silu_fwd(const void* h, const float* coef, void* y, int64_t M, int64_t d, sconf_stream_t stream);
+/* Launch geometry the conv-module kernels take for a problem (bookkeeping for tests and benchmarks, in the manner of
+ * sconf_gemm_variant): frames per time tile of sconf_glu_dwconv_fwd and of the second pass of sconf_convmod_bwd (8, 16, 32 or 64),
+ * and rows per thread of the backward's statistics pass (same steps); -1 = invalid arguments. */
+int sconf_convmod_tile_frames(int64_t B, int64_t N, int64_t d);
+int sconf_convmod_bwd_rows_per_thread(int64_t B, int64_t N, int64_t d);
 int64_t sconf_convmod_bwd_workspace(int64_t B, int64_t N, int64_t d, int64_t ksize, int colsum);
 int sconf_convmod_bwd(const void* dy, const void* h, const void* g, const int32_t* lengths, const float* w,
                       const float* brn_weight, const float* coef, double* red, float* bcoef, void* dg, float* dw,

@@ -1264,6 +1264,15 @@ bool use_wide(int64_t D, int64_t N, const int64_t* strides, int nviews) {
 
 }  // namespace
 
+// Which kernel set sconf_attn_fwd / sconf_attn_bwd run for a problem (bookkeeping for tests and benchmarks, in the manner of
+// sconf_gemm_variant): 8 = the 8-wave kernels, 4 = the 4-wave ones, -1 = unsupported head_dim.  token_stride: the largest token
+// stride (elements) among the views of the call.  Same decision code as the launches (reads SCONF_ATTN_WIDE per call).
+SCONF_API int sconf_attn_waves(int64_t D, int64_t N, int64_t token_stride) {
+    if (!(D == 32 || D == 64 || D == 128 || D == 256) || N <= 0) return -1;
+    const int64_t view[3] = {0, token_stride, 0};
+    return use_wide(D, N, view, 1) ? 8 : 4;
+}
+
 // q,k,v,o: bf16 (B,N,H,D) strided views (stride_b, stride_n, stride_h in elements; d contiguous).
 // lengths: int32 [B] or null — keys >= length are masked and query rows >= length are written as zeros
 // (attention.py:546-547).  lse: f32 (B,H,N) or null.  window -1 = unbounded.

@@ -407,6 +407,17 @@ static ConvmodBwdGeo convmod_bwd_geo(long B, long N, long d, long ksize, bool co
     q.gst = d + ksize * d + (colsum ? 2 * d : 0);           // slab row: [dbias d | dw K*d | dg_colsum 2d]
     return q;
 }
+// Bookkeeping (tests, benchmarks): the launch geometry the two sliding-window kernels and the statistics pass of the backward take
+// for a problem - frames per time tile (TN: 8, 16, 32 or 64) and rows per thread of brn_bwd_reduce_kernel (rpt, same steps).
+// -1: invalid arguments.  Same decision code as the launches.
+SCONF_API int sconf_convmod_tile_frames(int64_t B, int64_t N, int64_t d) {
+    if (B <= 0 || N <= 0 || d <= 0 || d % CV != 0) return -1;
+    return pick_tn(B, N, d / CV);
+}
+SCONF_API int sconf_convmod_bwd_rows_per_thread(int64_t B, int64_t N, int64_t d) {
+    if (B <= 0 || N <= 0 || d <= 0 || d % CV != 0) return -1;
+    return convmod_bwd_geo(B, N, d, 9, false).rpt;
+}
 // bytes of workspace sconf_convmod_bwd needs (the two slabs use it one after the other)
 SCONF_API int64_t sconf_convmod_bwd_workspace(int64_t B, int64_t N, int64_t d, int64_t ksize, int colsum) {
     if (B * N == 0 || d % CV != 0) return 0;

@@ -13,11 +13,9 @@ import torch
 
 import kernel_refs as R
 from conftest import load_golden
+from kernel_test_utils import BF, F32, TOL_BF16, TOL_F32, close, dev, rnd
 
 pytestmark = pytest.mark.gpu
-
-BF, F32 = torch.bfloat16, torch.float32
-TOL_F32, TOL_BF16 = 2e-3, 1.2e-2
 
 
 @pytest.fixture(scope='module')
@@ -27,26 +25,6 @@ def ops():
     import lcasr_amd.hip.ops as o
     o._lib.load()
     return o
-
-
-def dev(t):
-    return t.cuda() if isinstance(t, torch.Tensor) else t
-
-
-def close(out, ref, tol=None, name='', floor=0.0):
-    assert out.shape == ref.shape, f'{name}: shape {tuple(out.shape)} vs {tuple(ref.shape)}'
-    if tol is None:
-        tol = TOL_BF16 if out.dtype == BF else TOL_F32
-    o, r = out.detach().float().cpu(), ref.detach().float().cpu()
-    assert torch.isfinite(o).all(), f'{name}: non-finite output'
-    scale = max(float(r.abs().max()), floor) + 1e-12
-    err = float((o - r).abs().max()) / scale
-    assert err <= tol, f'{name}: max err {err:.3e} of max|ref|={scale:.3e} > {tol}'
-
-
-def rnd(*shape, dtype=BF, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed + sum(shape))
-    return (torch.randn(*shape, generator=g) * scale).to(dtype)
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
@@ -248,8 +226,9 @@ def test_norm_fwd_bwd(ops, mode, d):
 def test_norm2_fwd_bwd(ops, d, twice):
     """Two (twice: three, the last two with the same parameters - the head's legacy double norm) LayerNorms in one pass: against
     the single-norm kernels (same arithmetic; hipcc contracts the normalisation differently in the two kernels, so the last f32
-    bit may differ) and against the torch reference."""
-    M = 1029                                              # several rows per wave of the persistent backward, ragged tail
+    bit may differ) and against the torch reference.  M = 1029 is below 8 rows x one workgroup per CU: every wave of the persistent
+    backward owns ONE row here; the several-rows-per-wave branch is covered in test_kernel_geometry_gpu.py."""
+    M = 1029                                              # not a multiple of the 8 rows of a workgroup: a ragged last workgroup
     x = rnd(M, d, dtype=F32, scale=2.0) + 0.5
     w1 = rnd(d, dtype=F32, seed=1) * 0.1 + 1.0; b1 = rnd(d, dtype=F32, seed=2) * 0.1
     w2 = rnd(d, dtype=F32, seed=5) * 0.1 + 1.0; b2 = rnd(d, dtype=F32, seed=6) * 0.1
