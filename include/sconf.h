@@ -197,6 +197,9 @@ int sconf_sub_stage01_fwd(const void* x, int x_dtype, const float* w0, const flo
                           void* d1, int64_t B, int64_t F, int64_t T, int64_t C, sconf_stream_t stream);
 /* the MFMA backward sums the gradients in a fixed order through the workspace (sconf_sub_stage01_bwd_workspace bytes; 0 when
  * the shape goes to the VALU kernel, whose sums are atomic) */
+/* Channels split over workgroups in slabs (<= 512 channels each; C <= 512 is one slab): the number of slabs the MFMA kernel of
+ * the forward (bwd = 0) or backward takes for F mel bins and C channels, 0 when it does not take the shape.  Launches nothing. */
+int sconf_sub_stage01_slabs(int64_t F, int64_t C, int bwd);
 int64_t sconf_sub_stage01_bwd_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
 int sconf_sub_stage01_bwd(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
                           float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,

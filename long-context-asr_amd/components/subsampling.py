@@ -1,7 +1,7 @@
 """ConvSubsampling, 'dw_striding' mode (lcasr/components/subsampling.py:165-428, calc_length :557-567).
 
-`conv` is the same nn.Sequential of Conv2d/SiLU modules as the reference (state_dict keys conv.{0,2,3,5,6});
-they are parameter containers: the math runs channels-last in csrc/subsample.hip + GEMMs."""
+`conv` is the same nn.Sequential of Conv2d/SiLU modules as the reference (state_dict keys conv.{0,2,3,5,6}; conv.{0,2,3} at
+subsampling_factor 4); they are parameter containers: the math runs channels-last in csrc/subsample.hip + GEMMs."""
 import math
 
 import torch
@@ -26,12 +26,12 @@ class ConvSubsampling(nn.Module):
         super().__init__()
         if subsampling != 'dw_striding':
             raise NotImplementedError("only subsampling='dw_striding' is on the SConformerXL hot path (SURVEY.md §2 #2)")
-        if subsampling_factor != 8:
-            raise NotImplementedError('only subsampling_factor=8 (three stride-2 stages) is implemented')
+        if subsampling_factor < 1 or subsampling_factor & (subsampling_factor - 1) or subsampling_factor % 2 != 0:
+            raise ValueError('Sampling factor should be a multiply of 2!')      # the reference's message; it takes powers of 2
+        if subsampling_factor not in (4, 8):
+            raise NotImplementedError('subsampling_factor 4 and 8 (two / three stride-2 stages: the paper configs) are implemented')
         if is_causal:
             raise NotImplementedError('causal subsampling is not on the hot path')
-        if subsampling_factor % 2 != 0:
-            raise ValueError('Sampling factor should be a multiply of 2!')
         if not isinstance(activation, nn.SiLU):
             raise NotImplementedError("only subsampling_act='silu' is implemented")
         self._subsampling, self._conv_channels, self._feat_in, self._feat_out = subsampling, conv_channels, feat_in, feat_out
@@ -55,8 +55,12 @@ class ConvSubsampling(nn.Module):
         """x: (B, T, feat) as in the reference (the model transposes before the call); returns (B,N,d) f32, lengths."""
         lengths = calc_length(lengths, 2, 3, 2, False, self._sampling_num)
         c = self.conv
-        y = Fn.subsample(x.transpose(1, 2), c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[3].weight, c[3].bias,
-                         c[5].weight, c[5].bias, c[6].weight, c[6].bias, self.out.weight, self.out.bias)
+        if self._sampling_num == 2:
+            y = Fn.subsample4(x.transpose(1, 2), c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[3].weight, c[3].bias,
+                              self.out.weight, self.out.bias)
+        else:
+            y = Fn.subsample(x.transpose(1, 2), c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[3].weight, c[3].bias,
+                             c[5].weight, c[5].bias, c[6].weight, c[6].bias, self.out.weight, self.out.bias)
         if self.has_norm_out:
             y = self.norm_out(y)
         return y, lengths

@@ -549,6 +549,7 @@ int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const fl
                            float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
 int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
+int stage01_mfma_slabs(int64_t F, int64_t C, int bwd);
 namespace {
 
 struct LaunchGeo { int PL, iters, threads; dim3 grid; };
@@ -696,6 +697,10 @@ SCONF_API int sconf_sub_stage01_fwd(const void* x, int x_dtype, const float* w0,
     SCONF_LAUNCH_OK("sconf_sub_stage01_fwd");
     return 0;
 }
+
+// The number of channel slabs (the third grid dimension) the MFMA kernel of the fused stage uses for F mel bins and C channels,
+// forward (bwd == 0) or backward; 0 when that kernel does not take the shape.  Read-only: launches nothing.
+SCONF_API int sconf_sub_stage01_slabs(int64_t F, int64_t C, int bwd) { return stage01_mfma_slabs(F, C, bwd); }
 
 // Backward of the fused stage: parameter gradients of conv0 and of the first depthwise conv from dd1 (B,T4,F4,C) bf16;
 // all four outputs ACCUMULATED (+=).  (The mel input needs no gradient.)

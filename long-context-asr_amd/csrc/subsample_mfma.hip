@@ -14,7 +14,13 @@
 //     adjacent frequency bins, so the depthwise conv is v_dot2c_f32_bf16 on whole pairs (no unpacking);
 //   * backward: dW0^T[k][c] += patch^T . dP is again an MFMA (A = hardware-transposed read of the same im2col rows, B = the
 //     packed dP accumulator), and because column 9 of the patch is 1.0 its row 9 IS the bias gradient.
-// Taken when C % 32 == 0 and F/2 <= 64 positions (the paper configs: F = 80, C = 256 / 512); other shapes keep subsample.hip.
+// Taken when C % 32 == 0 and F/2 <= 64 positions (the paper configs: F = 80, C = 256 / 512 / 768); other shapes keep subsample.hip.
+//
+// Channel slabs: conv0, SiLU and the depthwise conv are all per-channel, so gridDim.z splits the channels into slabs of Cs
+// (a multiple of 32, <= 512; the last one may be narrower).  A workgroup sizes its LDS images and its wave -> channel-block map
+// by ITS slab's width and only the HBM addresses keep the row stride C (+ the slab's channel base).  C <= 512 is one slab - the
+// launch the kernels always had; wider subsamplers (the paper's 4x models: C = d_model = 768) need the split because neither the
+// forward's 3-row window (3 (F/4 + 2) (4 C + 128) bytes: 211 KB at C = 768, F = 80) nor the backward's dd1 image fits LDS.
 #include "common.h"
 #include <stdlib.h>
 
@@ -78,23 +84,25 @@ __device__ __forceinline__ bf16x8 w0_frag(const float* __restrict__ w0g, const f
 
 // ================================================================================================================
 // forward: d1[t4][f4][c] = bd[c] + sum_ij wd[c][i][j] * SiLU(conv0(x))[2t4+i-1][2f4+j-1][c]
-// grid (ceil(T4 / rows_per_block), B), 512 threads: wave w owns the channel blocks w, w+8, ...
+// grid (ceil(T4 / rows_per_block), B, channel slabs), 512 threads: wave w owns the channel blocks w, w+8, ... of its slab
 // LDS: patch[2] | act[3 slots][NPAIR][QS]: stage-0 activations of conv0 row t2 in slot t2 mod 3 as bf16 pairs (f2, f2+1) per
-// channel, pair index q = (f2 + 2) >> 1 (pair 0 = the zero padding at f2 = -1), QS = 4 C + 128 bytes (the 128 spread the four
+// channel, pair index q = (f2 + 2) >> 1 (pair 0 = the zero padding at f2 = -1), QS = 4 Cl + 128 bytes (the 128 spread the four
 // 16-lane groups of the depthwise read over all banks).
 // ================================================================================================================
-template <typename TX, int NCB>      // NCB = channel blocks per wave (1: C <= 256, 2: C <= 512)
+template <typename TX, int NCB>      // NCB = channel blocks per wave (1: slab <= 256 channels, 2: <= 512)
 __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_fwd_mfma_kernel(const TX* __restrict__ x, const float* __restrict__ w0g, const float* __restrict__ b0g,
                                                                   const float* __restrict__ wdg, const float* __restrict__ bdg, bf16* __restrict__ d1,
-                                                                  int F, int T, int C, int T2, int F2, int T4, int F4, int rows_per_block) {
+                                                                  int F, int T, int C, int Cs, int T2, int F2, int T4, int F4, int rows_per_block) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int NPAIR = F2 / 2 + 2, QS = 4 * C + 128, SLOT = NPAIR * QS;
+    const int cbase = blockIdx.z * Cs, Cl = min(Cs, C - cbase);      // this workgroup's channel slab [cbase, cbase + Cl)
+    w0g += cbase * 9; b0g += cbase; wdg += cbase * 9; bdg += cbase; d1 += cbase;   // from here on channel indices are slab-local
+    const int NPAIR = F2 / 2 + 2, QS = 4 * Cl + 128, SLOT = NPAIR * QS;
     char* patch = smem;                                  // [2][PATCH_BYTES]
     char* act = smem + 2 * PATCH_BYTES;                  // [3][NPAIR][QS]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5, cl = lane & 31;
     const int b = blockIdx.y;
     const TX* xb = x + (long)b * F * T;
-    const int ncb = C / 32;
+    const int ncb = Cl / 32;
 
     bf16x8 wf[NCB];
     unsigned wj0[NCB][3][2], wj12[NCB][3][2];            // depthwise taps as bf16 pairs: (0, w[i][0]) and (w[i][1], w[i][2]), 2 channels
@@ -278,34 +286,43 @@ __global__ __launch_bounds__(512, 4) void dwconv_window_fwd_kernel(const bf16* _
 
 // ================================================================================================================
 // backward: parameter gradients of conv0 (dw0, db0) and of the first depthwise conv (dwd, dbd) from dd1 (B,T4,F4,C), one pass over
-// the conv0 positions.  grid (ceil(T2 / rows_per_block), B), 512 threads, rows_per_block even; wave w owns channel blocks w, w+8.
+// the conv0 positions.  grid (ceil(T2 / rows_per_block), B, channel slabs), 512 threads, rows_per_block even; wave w owns channel
+// blocks w, w+8 of its slab of Cl channels.
 // Per conv0 row t2 and channel block:   pre = patch . W0^T (MFMA)  ->  sg = sigmoid(pre), s = pre sg
 //   for the (i, j) with 2 to + i - 1 = t2, 2 fo + j - 1 = f2:  g = dd1[to][fo];  gs += wd[i][j] g;  dwd[i][j] += g s;  dbd += g at (1,1)
 //   dp = gs sg (1 + pre (1 - sg));   dW0^T[k][c] += sum_pos patch[pos][k] dp[pos][c]  (MFMA; k = 9 is the 1.0 column: db0)
 // The accumulator layout gives a lane ONE channel and 16 positions, 4 consecutive f2 per register group: which taps an element
 // has is known at compile time from the register index (f2 parity) and one uniform branch per row (t2 parity).
-// LDS: patch[2] | gimg[2 slots = to & 1][F4][C] bf16 = the dd1 rows in use, copied by LDS-DMA.
+// LDS: patch[2] | gimg[2 slots = to & 1][F4][Cl] bf16 = the slab's columns of the dd1 rows in use, copied by LDS-DMA.
 // ================================================================================================================
 template <typename TX, int NCB>
 __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kernel(const TX* __restrict__ x, const float* __restrict__ w0g, const float* __restrict__ b0g,
                                                                   const float* __restrict__ wdg, const bf16* __restrict__ dd1,
                                                                   float* __restrict__ dw0, float* __restrict__ db0, float* __restrict__ dwd, float* __restrict__ dbd,
-                                                                  int F, int T, int C, int T2, int F2, int T4, int F4, int rows_per_block,
+                                                                  int F, int T, int C, int Cs, int T2, int F2, int T4, int F4, int rows_per_block,
                                                                   long det_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    {   // the parameter gradients go to this workgroup's row of a fixed-order slab (common.h)
+    const int cbase = blockIdx.z * Cs, Cl = min(Cs, C - cbase);      // this workgroup's channel slab [cbase, cbase + Cl)
+    {   // the parameter gradients go to this workgroup's row of a fixed-order slab (common.h); the channel slabs of one
+        // (row block, batch item) share that row and write disjoint column ranges of it
         const long drow = ((long)blockIdx.y * gridDim.x + blockIdx.x) * det_stride;
-        dw0 += drow; db0 += drow; dwd += drow; dbd += drow;
+        dw0 += drow + cbase * 9; db0 += drow + cbase; dwd += drow + cbase * 9; dbd += drow + cbase;
     }
-    const int GS = 2 * C, GSLOT = (F4 + 2) * GS;          // a dd1 row + two zero bins (fo = F4, F4 + 1: taps past the last output)
+    w0g += cbase * 9; b0g += cbase; wdg += cbase * 9;                // from here on channel indices are slab-local
+    const int GS = 2 * Cl, GSLOT = (F4 + 2) * GS;          // a dd1 row + two zero bins (fo = F4, F4 + 1: taps past the last output)
     char* patch = smem;                                  // [2][PATCH_BYTES]
-    char* gimg = smem + 2 * PATCH_BYTES;                 // [3][F4 + 2][C] bf16: slots to & 1, slot 2 = zeros (rows outside [0, T4))
+    char* gimg = smem + 2 * PATCH_BYTES;                 // [3][F4 + 2][Cl] bf16: slots to & 1, slot 2 = zeros (rows outside [0, T4))
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5, cl = lane & 31;
     const int b = blockIdx.y;
     const TX* xb = x + (long)b * F * T;
-    const bf16* gb = dd1 + (long)b * T4 * F4 * C;
-    const int ncb = C / 32;
+    const bf16* gb = dd1 + (long)b * T4 * F4 * C + cbase;
+    const int ncb = Cl / 32;
 
+    // The forward multiplies by the depthwise taps as bf16 (v_dot2c operands), so the gradient of what it computed carries the ROUNDED
+    // taps.  The slab form (C > 512) does that; with f32 taps here dw0 / db0 sit 4-5e-3 of their max away from it whatever the batch
+    // (the difference is coherent per channel, it does not average out).  A single slab keeps the f32 taps it always had, so the
+    // C <= 512 configurations stay bit-for-bit what they were.
+    const bool qtaps = gridDim.z > 1;
     bf16x8 wf[NCB];
     float wd[NCB][9], gwd[NCB][9], gbd[NCB];
     f32x16 aw0[NCB];                                     // dW0^T[k][c] (row 9 = db0)
@@ -315,20 +332,20 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
         wf[u] = w0_frag(w0g, b0g, c, hh);
         gbd[u] = 0.f;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { wd[u][k] = wdg[c * 9 + k]; gwd[u][k] = 0.f; }
+        for (int k = 0; k < 9; ++k) { const float w = wdg[c * 9 + k]; wd[u][k] = qtaps ? (float)(bf16)w : w; gwd[u][k] = 0.f; }
 #pragma unroll
         for (int r = 0; r < 16; ++r) aw0[u][r] = 0.f;
     }
     if (tid < 2 * PK / 2) *reinterpret_cast<unsigned*>(patch + (tid / (PK / 2)) * PATCH_BYTES + PPOS * PK * 2 + (tid % (PK / 2)) * 4) = 0u;
 
-    // one dd1 row `to` ([F4][C] bf16, contiguous) -> LDS slot to & 1 by LDS-DMA issued from inline asm (no staging registers, no
+    // the slab's columns of one dd1 row `to` (F4 segments of 2 Cl bytes, C elements apart; dense in LDS) -> LDS slot to & 1 by LDS-DMA issued from inline asm (no staging registers, no
     // ds_write, invisible to hipcc's vmcnt bookkeeping: waited for by hand before the barrier that publishes it).  Rows outside
     // [0, T4) are not copied: their users read the all-zero slot 2; bins >= F4 of every slot stay zero (set once below) - so the
     // tap reads need neither clamps nor selects.
     for (int i = tid; i < 3 * GSLOT / 4; i += 512) *reinterpret_cast<unsigned*>(gimg + i * 4) = 0u;
     __syncthreads();                                     // before any wave's DMA can land in a slot another wave is still zeroing
     const unsigned lds_g = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)gimg);
-    const int gchunks = F4 * C / 8;                       // 16-byte pieces per row
+    const int gseg = Cl / 8, gchunks = F4 * gseg;         // 16-byte pieces per segment / per row
     auto gissue = [&](int to) {
         if (to < 0 || to >= T4) return;                                        // uniform
         const bf16* src = gb + (long)to * F4 * C;
@@ -338,7 +355,7 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
             if (ch < gchunks) {                                                // lanes past the row stay out (the zero bins follow it)
                 unsigned keep;
                 asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src + (long)ch * 8), "s"(dst + (unsigned)(i * 512 * 16)) : "memory");
+                             : "=&s"(keep) : "v"(src + (long)(ch / gseg) * C + (ch % gseg) * 8), "s"(dst + (unsigned)(i * 512 * 16)) : "memory");
             }
         }
     };
@@ -384,8 +401,8 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
                     auto taps = [&](const char* grow, int i) {   // one dd1 row, tap row i: fo = 2p, 2p+1, 2p+2 serve f2 = base..base+3
                         const unsigned short* gp_ = reinterpret_cast<const unsigned short*>(grow + (2 * p) * GS + c * 2);
                         const float g0 = __builtin_bit_cast(float, (unsigned)gp_[0] << 16);
-                        const float g1 = __builtin_bit_cast(float, (unsigned)gp_[C] << 16);
-                        const float g2 = __builtin_bit_cast(float, (unsigned)gp_[2 * C] << 16);
+                        const float g1 = __builtin_bit_cast(float, (unsigned)gp_[Cl] << 16);
+                        const float g2 = __builtin_bit_cast(float, (unsigned)gp_[2 * Cl] << 16);
                         const float* w = wd[u] + 3 * i;
                         float* gw = gwd[u] + 3 * i;
                         // f2 = base   (even): j = 1, fo = 2p        f2 = base+1 (odd): j = 0, fo = 2p+1;  j = 2, fo = 2p
@@ -447,48 +464,71 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
 
 }  // namespace
 
+// LDS bytes of the two kernels for a slab of cs channels
+static size_t stage01_fwd_lds(int F2, long cs) { return 2 * (size_t)PATCH_BYTES + 3 * (size_t)(F2 / 2 + 2) * (4 * cs + 128); }
+static size_t stage01_bwd_lds(int F4, long cs) { return 2 * (size_t)PATCH_BYTES + 3 * (size_t)(F4 + 2) * 2 * cs; }
+constexpr size_t FWD_LDS_MAX = 160 * 1024, BWD_LDS_MAX = 80 * 1024;                            // backward: two workgroups per CU
+
+// Channels per slab (0: the MFMA kernels do not take the shape).  C <= 512 is ONE slab, or not taken when its LDS does not fit - the
+// launch those shapes always had.  Wider stages are cut into slabs of 256 channels: one 32-channel block for each of the 8 waves (no
+// wave idles while another does a second block, as with 384 = 12 blocks) and small enough an LDS image for two workgroups per CU in the
+// forward as well; measured against 2 x 384 at C = 768 in DESIGN.md section 7.  The last slab may be narrower (576 = 256 + 256 + 64).
+static int stage01_slab_channels(long F, long C, bool bwd) {
+    const int F2 = (int)((F - 1) / 2 + 1), F4 = (F2 - 1) / 2 + 1;
+    if (C <= 0 || C % 32 != 0 || C > 1024 || F2 > PPOS) return 0;
+    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return 0;                   // A/B switch
+    auto fits = [&](long cs) { return bwd ? stage01_bwd_lds(F4, cs) <= BWD_LDS_MAX : stage01_fwd_lds(F2, cs) <= FWD_LDS_MAX; };
+    if (C <= 512) return fits(C) ? (int)C : 0;
+    long cs = 256;
+    if (const char* e = getenv("SCONF_SUB_SLAB")) { const long v = atol(e); if (v >= 32 && v <= 512 && v % 32 == 0) cs = v; }   // tuning
+    while (cs > 32 && !fits(cs)) cs -= 32;
+    return fits(cs) ? (int)cs : 0;
+}
+// the number of channel slabs the MFMA kernel of this direction uses (0: it does not take the shape)
+int stage01_mfma_slabs(int64_t F, int64_t C, int bwd) {
+    const int cs = stage01_slab_channels(F, C, bwd != 0);
+    return cs ? (int)cdiv(C, (long)cs) : 0;
+}
+
 // returns 1 if the MFMA kernels took the problem, 0 if the caller should use the VALU kernels of subsample.hip
 int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const float* b0, const float* wd, const float* bd, void* d1,
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
-    if (C % 32 != 0 || C > 512 || F2 > PPOS) return 0;
-    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return 0;                   // A/B switch
-    const size_t sh = 2 * (size_t)PATCH_BYTES + 3 * (size_t)(F2 / 2 + 2) * (4 * C + 128);
-    if (sh > 160 * 1024) return 0;
+    const int Cs = stage01_slab_channels(F, C, false);
+    if (!Cs) return 0;
+    const size_t sh = stage01_fwd_lds(F2, Cs);
     long target = 4096;
     if (const char* e = getenv("SCONF_SUB_FWD_BLOCKS")) target = atol(e);                       // tuning
     const int rpb = std::max(1, (int)cdiv((long)T4 * B, target));
-    dim3 grid(cdiv(T4, rpb), (unsigned)B), block(512);
+    dim3 grid(cdiv(T4, rpb), (unsigned)B, (unsigned)cdiv(C, (long)Cs)), block(512);
 #define LF(TX, NCB_) do { \
         static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_fwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL((stage01_fwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, bd, (bf16*)d1, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb); } while (0)
-    if (x_dtype == SCONF_F32) { if (C <= 256) LF(float, 1); else LF(float, 2); }
-    else                      { if (C <= 256) LF(bf16, 1); else LF(bf16, 2); }
+        if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_fwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FWD_LDS_MAX); attr = true; } \
+        hipLaunchKernelGGL((stage01_fwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, bd, (bf16*)d1, (int)F, (int)T, (int)C, Cs, T2, F2, T4, F4, rpb); } while (0)
+    if (x_dtype == SCONF_F32) { if (Cs <= 256) LF(float, 1); else LF(float, 2); }
+    else                      { if (Cs <= 256) LF(bf16, 1); else LF(bf16, 2); }
 #undef LF
     return 1;
 }
 
 // whether the MFMA backward takes this shape, and its launch geometry
-static bool stage01_bwd_mfma_geo(long B, long F, long T, long C, dim3& grid, size_t& sh, int& rpb) {
+static bool stage01_bwd_mfma_geo(long B, long F, long T, long C, dim3& grid, size_t& sh, int& rpb, int& Cs) {
     const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), F4 = (F2 - 1) / 2 + 1;
-    if (C % 32 != 0 || C > 512 || F2 > PPOS) return false;
-    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return false;               // A/B switch
-    if ((F4 * C) % 8 != 0) return false;
-    const size_t gslot = (size_t)(F4 + 2) * 2 * C;
-    sh = 2 * (size_t)PATCH_BYTES + 3 * gslot;
-    if (sh > 80 * 1024) return false;                                                           // two workgroups per CU
+    Cs = stage01_slab_channels(F, C, true);
+    if (!Cs) return false;
+    sh = stage01_bwd_lds(F4, Cs);
     long target = 2048;
     if (const char* e = getenv("SCONF_SUB_BWD_BLOCKS")) target = atol(e);                       // tuning
     rpb = std::max(2, (int)cdiv((long)T2 * B, target));
     rpb += rpb & 1;                                                                              // even: a block starts on an even conv0 row
-    grid = dim3(cdiv(T2, rpb), (unsigned)B);
+    grid = dim3(cdiv(T2, rpb), (unsigned)B, (unsigned)cdiv(C, (long)Cs));
     return true;
 }
-// bytes of workspace the MFMA backward needs (0: it does not take this shape): one slab row of 20C f32 per workgroup
+// bytes of workspace the MFMA backward needs (0: it does not take this shape): one row of 20C f32 per (row block, batch item),
+// shared by that workgroup row's channel slabs
 int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C) {
-    dim3 grid; size_t sh; int rpb;
-    if (B * T * F == 0 || !stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb)) return 0;
+    dim3 grid; size_t sh; int rpb, Cs;
+    if (B * T * F == 0 || !stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb, Cs)) return 0;
     return (int64_t)grid.x * grid.y * 20 * C * 4;
 }
 
@@ -497,18 +537,18 @@ int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const fl
                            float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
-    dim3 grid; size_t sh; int rpb;
-    if (!stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb)) return 0;
+    dim3 grid; size_t sh; int rpb, Cs;
+    if (!stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb, Cs)) return 0;
     const dim3 block(512);
-    // slab row: [dw0 9C | db0 C | dwd 9C | dbd C], added into the gradients in workgroup order after the kernel
+    // workspace row: [dw0 9C | db0 C | dwd 9C | dbd C], added into the gradients in workgroup-row order after the kernel
     const long rows = (long)grid.x * grid.y, dst = 20 * C;
     float* sl = det_begin<float>(workspace, workspace_bytes, rows, dst, stream);
     if (!sl) { sconf_set_error("sconf_sub_stage01_bwd: needs %ld bytes of workspace (sconf_sub_stage01_bwd_workspace)", rows * dst * 4); return -1; }
 #define LB(TX, NCB_) do { \
-        if (sh > 64 * 1024) { static bool attr = false; if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_bwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } } \
-        hipLaunchKernelGGL((stage01_bwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, (const bf16*)dd1, sl, sl + 9 * C, sl + 10 * C, sl + 19 * C, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb, dst); } while (0)
-    if (x_dtype == SCONF_F32) { if (C <= 256) LB(float, 1); else LB(float, 2); }
-    else                      { if (C <= 256) LB(bf16, 1); else LB(bf16, 2); }
+        if (sh > 64 * 1024) { static bool attr = false; if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_bwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_MAX); attr = true; } } \
+        hipLaunchKernelGGL((stage01_bwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, (const bf16*)dd1, sl, sl + 9 * C, sl + 10 * C, sl + 19 * C, (int)F, (int)T, (int)C, Cs, T2, F2, T4, F4, rpb, dst); } while (0)
+    if (x_dtype == SCONF_F32) { if (Cs <= 256) LB(float, 1); else LB(float, 2); }
+    else                      { if (Cs <= 256) LB(bf16, 1); else LB(bf16, 2); }
 #undef LB
     det_finish<float>(sl, rows, dst, DetSegs<float>{{dw0, db0, dwd, dbd}, {0, 9 * C, 10 * C, 19 * C}, {9 * C, C, 9 * C, C}, 4}, stream);
     return 1;

@@ -707,7 +707,7 @@ def decoder_head_ctc(x, nw, nb, wff, bff, B, targets, input_lengths, target_leng
 
 
 # =================================================================================================
-# ConvSubsampling 'dw_striding' x8  — subsampling.py:276-321, 384-428
+# ConvSubsampling 'dw_striding' x8 and x4  — subsampling.py:276-321, 384-428
 # =================================================================================================
 class SubsampleFn(Function):
     @staticmethod
@@ -755,6 +755,48 @@ class SubsampleFn(Function):
 
 def subsample(audio, w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout):
     return SubsampleFn.apply(audio, w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout)
+
+
+class Subsample4Fn(Function):
+    """'dw_striding' x4 (two stride-2 stages, conv.{0,2,3}): the x8 chain cut after the first 1x1 conv - the fused stage 0 -> 1, the 1x1
+    GEMM, SiLU + transpose over the F/4 bins, the output GEMM."""
+
+    @staticmethod
+    def forward(ctx, audio, w0, b0, wd1, bd1, wp1, bp1, wout, bout):
+        audio = audio.contiguous()
+        B = audio.shape[0]
+        C = w0.shape[0]
+        w0f, wd1f = (t.detach().reshape(C, 9).contiguous() for t in (w0, wd1))
+        wp1h, woh = wcast(wp1), wcast(wout)
+        d1 = ops.sub_stage01_fwd(audio, w0f, b0, wd1f, bd1)                            # (B,N,F4,C); stage 0 never hits HBM
+        pre1 = ops.gemm(d1.view(-1, C), wp1h, 'nt', bias=bp1).view(d1.shape)
+        N, F4 = d1.shape[1], d1.shape[2]
+        s = ops.sub_silu_transpose(pre1.view(B * N, F4, C))                            # (B*N, C*F4)
+        x = ops.gemm(s, woh, 'nt', bias=bout, out_dtype=F32)
+        ctx.save_for_backward(audio, w0f, wd1f, wcast_t(wp1), wcast_t(wout), b0, d1, pre1, s)
+        ctx.P = (w0, b0, wd1, bd1, wp1, bp1, wout, bout)
+        return x.view(B, N, -1)
+
+    @staticmethod
+    def backward(ctx, dx):
+        pw0, pb0, pwd1, pbd1, pwp1, pbp1, pwo, pbo = ctx.P
+        audio, w0f, wd1f, wp1t, wot, b0, d1, pre1, s = ctx.saved_tensors
+        B, N, F4, C = d1.shape
+        dx16 = ops.cast(dx.contiguous().view(B * N, -1), BF16)
+        ds = ops.gemm(dx16, wot, 'nt')                                                 # (B*N, C*F4)
+        dwo = _wgrad(dx16, s, pwo)
+        dbo = _bgrad(dx16, pbo)
+        dpre1 = ops.sub_silu_transpose(pre1.view(B * N, F4, C), ds).view(-1, C)
+        dwp1 = _wgrad(dpre1, d1.view(-1, C), pwp1)
+        dbp1 = _bgrad(dpre1, pbp1)
+        dd1 = ops.gemm(dpre1, wp1t, 'nt').view(d1.shape)
+        dwd1, dbd1, dw0, db0 = _G(pwd1, (C, 9)), _G(pbd1), _G(pw0, (C, 9)), _G(pb0)
+        ops.sub_stage01_bwd_(dd1, audio, w0f, b0, wd1f, dw0.t, db0.t, dwd1.t, dbd1.t)  # conv0 recomputed; no (B,T/2,F/2,C) grads
+        return (None, dw0.out(), db0.out(), dwd1.out(), dbd1.out(), dwp1, dbp1, dwo, dbo)
+
+
+def subsample4(audio, w0, b0, wd1, bd1, wp1, bp1, wout, bout):
+    return Subsample4Fn.apply(audio, w0, b0, wd1, bd1, wp1, bp1, wout, bout)
 
 
 # =================================================================================================

@@ -521,6 +521,12 @@ def sub_stage01_fwd(x: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, wd: tor
     return d1
 
 
+def sub_stage01_slabs(F: int, C: int, bwd: bool = False) -> int:
+    """Channel slabs (workgroups along the channel axis) the MFMA kernel of the fused stage takes for F mel bins and C channels;
+    0 when it does not take the shape.  A host query: nothing is launched."""
+    return int(_lib.load().sconf_sub_stage01_slabs(int(F), int(C), int(bool(bwd))))
+
+
 def sub_stage01_bwd_(dd1: torch.Tensor, x: torch.Tensor, w0, b0, wd, dw0, db0, dwd, dbd) -> None:
     """Parameter gradients of the fused stage (accumulated in place) from dd1 (B,T4,F4,C) bf16."""
     _chk(dd1, 'dd1', torch.bfloat16); _chk(x, 'x')

@@ -18,12 +18,14 @@ from .optim import MADGRAD
 from .parallel import GradSync
 
 
-def synthetic_batch(B: int, T: int, vocab_size: int, seed: int = 0, device='cuda', dtype=torch.float32):
-    """mel ~ N(0,1) (B,80,T), lengths = T, targets uniform in [0,V), S = N/4 tokens per sample."""
+def synthetic_batch(B: int, T: int, vocab_size: int, seed: int = 0, device='cuda', dtype=torch.float32, subsampling_factor: int = 8):
+    """mel ~ N(0,1) (B,80,T), lengths = T, targets uniform in [0,V), S = N/4 tokens per sample
+    (N = the tokens the model's subsampler makes of T frames: one stride-2 stage per factor of 2)."""
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, 80, T, generator=g).to(dtype)
-    N = ((T - 1) // 2 + 1 - 1) // 2 + 1
-    N = (N - 1) // 2 + 1
+    N = T
+    for _ in range(int(subsampling_factor).bit_length() - 1):
+        N = (N - 1) // 2 + 1
     S = max(N // 4, 1)
     targets = torch.randint(0, vocab_size, (B, S), generator=g)
     return (x.to(device), torch.full((B,), T, dtype=torch.long, device=device), targets.to(device),

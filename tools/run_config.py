@@ -1,5 +1,5 @@
 """Run a few training steps of a BASELINE.json config on one GPU and print ms/step, frames/s, loss, peak memory.
-usage: python tools/run_config.py {c1|c2|c3|c4|c5|h12|h3} [batch] [steps]"""
+usage: python tools/run_config.py {c1|c2|c3|c4|c5|h12|h3|c4x|c4x_512} [batch] [steps]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,6 +18,12 @@ CFG = {
     'c4': (dict(base, n_layers=9, d_model=768, n_heads=6, head_dim=128, subsampling_conv_channels=256, checkpoint_every_n_layers=1, ff_checkpoint_lvl=2), 16384, 16),
     # exp_set_seq_rotary_base_3l_2048.yaml
     'c5': (dict(base, n_layers=3, d_model=2048, n_heads=16, head_dim=128, subsampling_conv_channels=512, ff_checkpoint_lvl=2), 131072, 2),
+    # exp_set_seq_rotary_base_4x_subample.yaml: subsampling_factor 4 (N = T/4 tokens), subsampler channels -1 -> d_model = 768
+    'c4x': (dict(base, n_layers=6, d_model=768, n_heads=6, head_dim=128, subsampling_factor=4, subsampling_conv_channels=-1,
+                 rotary_base_freq=10000000, checkpoint_every_n_layers=1, ff_checkpoint_lvl=2), 16384, 16),
+    # the same with 512 subsampler channels: separates the token count from the subsampler width
+    'c4x_512': (dict(base, n_layers=6, d_model=768, n_heads=6, head_dim=128, subsampling_factor=4, subsampling_conv_channels=512,
+                     rotary_base_freq=10000000, checkpoint_every_n_layers=1, ff_checkpoint_lvl=2), 16384, 16),
 }
 name = sys.argv[1]
 kw, T, B = CFG[name]
@@ -26,7 +32,7 @@ steps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 torch.manual_seed(12345)
 model = SCConformerXL(**kw).cuda().train()
 tr = Trainer(model, global_batch=B)
-batch = synthetic_batch(B, T, 4095)
+batch = synthetic_batch(B, T, 4095, subsampling_factor=kw.get('subsampling_factor', 8))
 losses = []
 for i in range(steps + 1):
     if i == 1:
