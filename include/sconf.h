@@ -243,6 +243,31 @@ int sconf_overlap_add_exp(const float* logp, int64_t W, int64_t n, int64_t C, in
 int sconf_overlap_finalize(const float* acc, const float* count, float* out, int64_t N, int64_t C, sconf_stream_t stream);
 /* idx[m] = argmax_c x[m][c], first index on ties: GreedyCTCDecoder.forward (lcasr/decoding/greedy.py:19). */
 int sconf_argmax_rows(const float* x, int64_t M, int64_t C, int32_t* idx, sconf_stream_t stream);
+/* Placement of the kept rows of buffered windows, fetch_logits (lcasr/eval/buffered_transcription.py:74-90): for the W windows of
+ * src (W,n,C) f32 and a device table spans (W,3) int32 of (src_row0, rows, dst_row0), dst (N,C) rows [dst_row0, dst_row0 + rows)
+ * = window w rows [src_row0, src_row0 + rows).  One launch per model batch; C % 4 == 0.  A span that runs past either buffer is
+ * refused on the device (the table is never read by the host): it copies nothing.  From sconf_version() 210. */
+int sconf_copy_row_spans(const float* src, int64_t W, int64_t n, int64_t C, const int32_t* spans, float* dst, int64_t N,
+                         sconf_stream_t stream);
+
+/* ---- Edit counts: the scoring under word_error_rate_detail (lcasr/eval/wer.py:5-73, there through jiwer).  From version 210. ----
+ * P ragged pairs of int32 id sequences: pair p is hyp[hyp_off[p] .. hyp_off[p+1]) against ref[ref_off[p] .. ref_off[p+1]); the
+ * offset arrays hold P + 1 exclusive prefix offsets (int64) and, like everything else, live on the device.  out (P,4) int64 =
+ * [errors, substitutions, deletions, insertions]: errors is the unit-cost Levenshtein distance, the split is that of the optimal
+ * alignment with the FEWEST substitutions, which is unique (ins - del = len(hyp) - len(ref), sub + del + ins = errors).  jiwer's
+ * split comes from one backtrace (RapidFuzz editops) and may be that of another, equally optimal alignment; the total cannot differ.
+ * One launch, one workgroup per pair, no host read; P == 0 launches nothing.  A reference longer than sconf_edit_pass_cols() ids
+ * parks one 8-byte key per hypothesis id between passes: pair p uses keys [hyp_off[p] - hyp_off[0] + p, ... + len(hyp_p) + 1) of the
+ * workspace, so 8 * (total hypothesis ids + P) bytes suffice and sconf_edit_counts_workspace returns the bound 8 * P * (max_hyp + 1)
+ * (0 while max_ref <= sconf_edit_pass_cols(); -1 for invalid sizes).  A pair whose keys do not fit gets out = -1,-1,-1,-1.
+ * Geometry queries: columns (reference ids) one wave holds, columns one pass of the workgroup holds, rows (hypothesis ids)
+ * between two barriers. */
+int sconf_edit_strip_cols(void);
+int sconf_edit_pass_cols(void);
+int sconf_edit_block_rows(void);
+int64_t sconf_edit_counts_workspace(int64_t P, int64_t max_hyp, int64_t max_ref);
+int sconf_edit_counts(const int32_t* hyp, const int64_t* hyp_off, const int32_t* ref, const int64_t* ref_off, int64_t P,
+                      int64_t* out, void* workspace, int64_t workspace_bytes, sconf_stream_t stream);
 
 /* ---- SpecAugment and dynamic evaluation (lcasr/utils/augmentation.py:10-100, lcasr/eval/dynamic_eval.py:11-142) -----------
  * sconf_spec_mask: dst (B,F,T) f32 = src (batch stride src_batch_stride elements; 0 broadcasts one spectrogram to every row of

@@ -1,6 +1,7 @@
 // Forward-only inference helpers for the sliding-window transcription path:
 //   * overlap-average of window posteriors   (lcasr/eval/utils.py:45-111, fetch_logits)
 //   * row argmax for greedy CTC decoding     (lcasr/decoding/greedy.py:9-23)
+//   * placement of the kept rows of buffered windows (lcasr/eval/buffered_transcription.py:74-90, fetch_logits)
 // All HBM-bound; one pass over the window log-probs.
 #include "common.h"
 #include <algorithm>
@@ -76,6 +77,19 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
     if (lane == 0) idx[row] = bi == 0x7fffffff ? 0 : bi;
 }
 
+// dst rows [dst_row0, dst_row0 + rows) = rows [src_row0, src_row0 + rows) of window blockIdx.x, for every window's span
+// (src_row0, rows, dst_row0).  A span that leaves either buffer copies nothing.
+__global__ __launch_bounds__(256) void copy_row_spans_kernel(const float* __restrict__ src, const int* __restrict__ spans,
+                                                            float* __restrict__ dst, long n, int C, long N) {
+    const long w = blockIdx.x;
+    const long s0 = spans[w * 3], rows = spans[w * 3 + 1], d0 = spans[w * 3 + 2];
+    if (s0 < 0 || rows <= 0 || d0 < 0 || s0 + rows > n || d0 + rows > N) return;
+    const float4* from = reinterpret_cast<const float4*>(src + (w * n + s0) * C);
+    float4* to = reinterpret_cast<float4*>(dst + d0 * C);
+    const long total = rows * (C / 4);
+    for (long idx = (long)blockIdx.y * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.y * blockDim.x) to[idx] = from[idx];
+}
+
 }  // namespace
 
 // acc (N,C) += sum over the windows covering each row of exp(logp); count (N) += number of covering windows.
@@ -112,5 +126,21 @@ SCONF_API int sconf_argmax_rows(const float* x, int64_t M, int64_t C, int32_t* i
     if (M == 0) return 0;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)cdiv(M, 4)), dim3(256), 0, stream, x, idx, (long)M, (int)C);
     SCONF_LAUNCH_OK("sconf_argmax_rows");
+    return 0;
+}
+
+// dst (N,C) rows [dst_row0, +rows) = src (W,n,C) window w rows [src_row0, +rows) for the W spans (src_row0, rows, dst_row0) of a
+// device int32 table: the slice assignment of the buffered fetch_logits (buffered_transcription.py:88) for a batch of windows.
+// The table stays on the device, so a span that runs past either buffer is refused there: it copies nothing.
+SCONF_API int sconf_copy_row_spans(const float* src, int64_t W, int64_t n, int64_t C, const int32_t* spans, float* dst, int64_t N,
+                                   hipStream_t stream) {
+    SCONF_REQUIRE(C % 4 == 0 && C > 0, "sconf_copy_row_spans: C=%ld must be a positive multiple of 4", (long)C);
+    SCONF_REQUIRE(W >= 0 && W < (1ll << 31) && n >= 0 && N >= 0, "sconf_copy_row_spans: size out of range");
+    if (W == 0 || n == 0 || N == 0) return 0;
+    SCONF_REQUIRE(src && spans && dst, "sconf_copy_row_spans: null pointer");
+    const int chunks = (int)std::min<long>(cdiv(n * (C / 4), 256), 64);
+    hipLaunchKernelGGL(copy_row_spans_kernel, dim3((unsigned)W, chunks), dim3(256), 0, stream, src, (const int*)spans, dst, (long)n, (int)C,
+                       (long)N);
+    SCONF_LAUNCH_OK("sconf_copy_row_spans");
     return 0;
 }

@@ -1,0 +1,72 @@
+"""Evaluation driver — the per-recording loop of eval/run.py:71-125 of the reference without its dataset loading.
+
+Four steps per recording, as there: log-probs in one of three modes, greedy CTC decoding, text normalisation, and
+word_error_rate_detail.  The modes are the reference's `--evaluation_mode` choices (run.py:37-44):
+  'averaged_moving_window'   eval.utils.fetch_logits: overlapping windows, posteriors averaged where they overlap;
+  'buffered'                 eval.buffered_transcription.fetch_logits: chunks transcribed inside a context buffer;
+  'windowed_attention'       one window over the whole recording (up to max_sequence_length frames) with every attention module
+                             limited to seq_len // subsampling_factor // 2 tokens to either side.  The reference sets this in the
+                             config before it builds the model; here the modules' windows are set for the duration of the call and
+                             restored afterwards, also when the model raises.
+The reference normalises with Whisper's EnglishTextNormalizer, which is not a dependency of this package: `normalize` defaults
+to the identity (`.lower()` is applied as in the reference)."""
+from __future__ import annotations
+
+from typing import Callable, Iterable, List, Optional, Tuple
+
+import torch
+
+from ..decoding.greedy import GreedyCTCDecoder
+from .buffered_transcription import fetch_logits as buffered_eval
+from .utils import fetch_logits as moving_average_eval
+from .wer import word_error_rate_detail
+
+MODES = ('averaged_moving_window', 'buffered', 'windowed_attention')
+
+
+class _Args:
+    """Stand-in for the reference's argparse namespace when the caller has none (seq_len / overlap of -1 then have no default)."""
+    def __init__(self):
+        self.config = {}
+
+
+def _windowed_modules(model) -> List[torch.nn.Module]:
+    return [m for m in model.modules() if hasattr(m, 'left_window') and hasattr(m, 'right_window')]
+
+
+def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
+             evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
+             include_per_recording_evaluations: bool = False, args=None) -> List[dict]:
+    """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
+    of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last."""
+    if evaluation_mode not in MODES:
+        raise ValueError(f'evaluation_mode must be one of {MODES}, got {evaluation_mode!r}')
+    args = _Args() if args is None else args
+    normalize = (lambda s: s) if normalize is None else normalize
+    eval_fn = buffered_eval if evaluation_mode == 'buffered' else moving_average_eval
+    decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)
+    modules = _windowed_modules(model) if evaluation_mode == 'windowed_attention' else []
+    saved = [(m.left_window, m.right_window) for m in modules]
+    all_texts, all_golds, wer_data = [], [], []
+    try:
+        if evaluation_mode == 'windowed_attention':
+            window = seq_len // model.subsampling.subsampling_factor // 2      # // 2: applied in both directions
+            for m in modules:
+                m.left_window = m.right_window = window
+            seq_len = int(getattr(args, 'max_sequence_length', 3600000))       # 10 hours
+        for rec_id, spec, gold_text in recordings:
+            logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer,
+                             use_tqdm=False, return_numpy=False)
+            out = normalize(decoder(logits)).lower()
+            all_texts.append(out)
+            all_golds.append(gold_text)
+            if include_per_recording_evaluations:
+                wer, words, ins_rate, del_rate, sub_rate = word_error_rate_detail(hypotheses=[out], references=[gold_text])
+                wer_data.append({'recording': rec_id, 'wer': wer, 'words': words, 'ins_rate': ins_rate, 'del_rate': del_rate,
+                                 'sub_rate': sub_rate})
+    finally:
+        for m, (lw, rw) in zip(modules, saved):
+            m.left_window, m.right_window = lw, rw
+    wer, words, ins_rate, del_rate, sub_rate = word_error_rate_detail(hypotheses=all_texts, references=all_golds)
+    wer_data.append({'recording': 'all', 'wer': wer, 'words': words, 'ins_rate': ins_rate, 'del_rate': del_rate, 'sub_rate': sub_rate})
+    return wer_data

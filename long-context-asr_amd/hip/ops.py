@@ -732,3 +732,34 @@ def ctc_collapse(x: torch.Tensor, lengths: Optional[torch.Tensor], blank: int, s
     tl = torch.empty(B, dtype=torch.int32, device=x.device)
     _lib.call('sconf_ctc_collapse', _p(x), B, N, Cc, _p(lengths), int(blank), _p(idx), _p(targets), s_cap, _p(tl), _stream())
     return targets, tl
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation loop: buffered-window placement and edit counts (plain references: tests/eval_refs.py)
+# ------------------------------------------------------------------------------------------------
+def copy_row_spans_(src: torch.Tensor, spans: torch.Tensor, dst: torch.Tensor) -> None:
+    """dst (N,C) rows [d0, d0 + rows) = src (W,n,C) window w rows [s0, s0 + rows) for the rows (s0, rows, d0) of spans (W,3) int32
+    on the device (in place, one launch).  A span that runs past either buffer copies nothing."""
+    _chk(src, 'src', torch.float32); _chk(spans, 'spans', torch.int32); _chk(dst, 'dst', torch.float32)
+    if src.dim() != 3 or dst.dim() != 2 or src.shape[2] != dst.shape[1]:
+        raise ValueError(f'src must be (windows, rows, C) and dst (N, C), got {tuple(src.shape)} / {tuple(dst.shape)}')
+    W, n, Cc = src.shape
+    if spans.shape != (W, 3): raise ValueError(f'spans must be ({W}, 3), got {tuple(spans.shape)}')
+    _lib.call('sconf_copy_row_spans', _p(src), W, n, Cc, _p(spans), _p(dst), dst.shape[0], _stream())
+
+
+def edit_counts(hyp: torch.Tensor, hyp_off: torch.Tensor, ref: torch.Tensor, ref_off: torch.Tensor) -> torch.Tensor:
+    """(P,4) int64 [errors, substitutions, deletions, insertions] of P ragged pairs: hyp / ref int32 ids, hyp_off / ref_off (P+1,)
+    int64 exclusive prefix offsets, all on the device; one launch, nothing read back.  errors is the Levenshtein distance; the
+    split is that of the optimal alignment with the fewest substitutions (unique; jiwer's backtrace may pick another optimal
+    alignment, with the same total).  A row of -1 marks a pair whose workspace did not fit (cannot happen through this wrapper)."""
+    _chk(hyp, 'hyp', torch.int32); _chk(ref, 'ref', torch.int32); _chk(hyp_off, 'hyp_off', torch.int64); _chk(ref_off, 'ref_off', torch.int64)
+    if hyp_off.dim() != 1 or hyp_off.shape != ref_off.shape or hyp_off.numel() < 1:
+        raise ValueError(f'hyp_off and ref_off must both be (P + 1,), got {tuple(hyp_off.shape)} / {tuple(ref_off.shape)}')
+    P = hyp_off.numel() - 1
+    out = torch.empty(P, 4, dtype=torch.int64, device=hyp_off.device)
+    # no pair is longer than its whole array: sized without reading the offsets (the kernel packs the parked columns by hyp_off)
+    nws = 8 * (hyp.numel() + P) if ref.numel() > int(_lib.load().sconf_edit_pass_cols()) else 0
+    ws = _workspace(nws, hyp_off.device) if nws else None
+    _lib.call('sconf_edit_counts', _p(hyp), _p(hyp_off), _p(ref), _p(ref_off), P, _p(out), _p(ws), nws, _stream())
+    return out
