@@ -156,6 +156,28 @@ int sconf_attn_bwd(const void* q, const void* k, const void* v, const void* o, c
                    const float* rot_cos /*nullable: f32 (N, D/2); with rot_sin: dq, dk come back as gradients of the UNROTATED q, k*/,
                    const float* rot_sin, sconf_stream_t stream);
 
+/* ---- Attention maps (lcasr/components/attention.py:424-445 ReturnAttention, 556-595 CollectAttentionProbs).  From version 220. ----
+ * q, k: bf16 (B,N,H,D) views with element strides {batch, token, head}, as sconf_attn_fwd takes them (the post-rotary blocks of the
+ * (B,N,3,H,D) buffer), 16-byte aligned, strides multiples of 8; D 32, 64, 128 or 256; lengths int32 [B] or NULL; win_left / win_right
+ * with sconf_attn_fwd's meaning (-1 = unbounded).  A position (i, j) is MASKED when j >= length, when j lies outside
+ * [i - win_left, i + win_right], or when i >= length.
+ * sconf_attn_scores: out (B,H,N,N), out_dtype SCONF_F32 or SCONF_BF16, = scale * q_i . k_j (MFMA, f32 accumulation), -inf at masked
+ * positions: the reference's `a_weight` (attention.py:431-434).  64-bit output indexing.
+ * sconf_attn_offset_profile: prof (B,H,2N-1) f32, prof[b,h,delta + N - 1] = sum over rows i of P[b,h,i,i + delta] with
+ * P = exp(scale * q_i . k_j - lse[b,h,i]) at unmasked positions and 0 elsewhere; lse (B,H,N) f32 is sconf_attn_fwd's output on the
+ * same operands, lengths and window (rows with lse = +inf contribute nothing).  No N x N buffer exists: a workgroup owns 224
+ * offsets x 512 query rows and writes one partial row to the workspace (sconf_attn_offset_profile_workspace bytes; with a window
+ * only offsets in [-win_left, win_right] have rows), a second kernel adds the rows of an offset in a fixed order: the same bits
+ * every call.  Offsets outside the window are written as 0. */
+int sconf_attn_scores(const void* q, const void* k, void* out, int out_dtype, const int32_t* lengths, int64_t B, int64_t N,
+                      int64_t H, int64_t D, const int64_t* q_strides /*host*/, const int64_t* k_strides /*host*/, int win_left,
+                      int win_right, float scale, sconf_stream_t stream);
+int64_t sconf_attn_offset_profile_workspace(int64_t B, int64_t N, int64_t H, int win_left, int win_right);
+int sconf_attn_offset_profile(const void* q, const void* k, const float* lse, float* prof, const int32_t* lengths, int64_t B,
+                              int64_t N, int64_t H, int64_t D, const int64_t* q_strides /*host*/, const int64_t* k_strides /*host*/,
+                              int win_left, int win_right, float scale, void* workspace, int64_t workspace_bytes,
+                              sconf_stream_t stream);
+
 /* Conformer conv module, token-major (convolution.py:103-124; conv1dFunc seam convolution.py:6-22; batchrenorm.py:52-92).
  * The statistics and parameter gradients are summed in a fixed order through the caller's workspace (sizes from the
  * *_workspace queries, in bytes): the same result every run. */

@@ -12,7 +12,7 @@ int sconf_set_error(const char* fmt, ...) {
 }
 
 SCONF_API const char* sconf_last_error(void) { return g_err; }
-SCONF_API int sconf_version(void) { return 210; }   // 0.2.1: edit counts, row-span placement (200: attention head_dim 64 and 256)
+SCONF_API int sconf_version(void) { return 220; }   // 0.2.2: attention scores and offset profile (210: edit counts, row-span placement; 200: attention head_dim 64 and 256)
 
 // Number of CUs of the current device (grid sizing on the host side).
 SCONF_API int sconf_num_cus(void) {

@@ -453,6 +453,33 @@ def attn_block(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D,
     return AttnBlockFn.apply(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, tuple(window), mode, eps, residual)
 
 
+def attn_block_observed(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, window, mode, eps, residual, observer, flag):
+    """The attention block with an observer (Attention.return_attention_weights / return_attention_offsets): the kernel sequence
+    of AttnBlockFn.forward outside autograd, then observer(q, k, lse, lengths, window) on the post-rotary q and k blocks of the
+    qkv buffer and the forward's row log-sum-exp.  The result is bit-equal to attn_block's.  Analysis only: there is no backward,
+    so it refuses to run where one would be recorded.  `flag` names the switch in the error."""
+    if torch.is_grad_enabled():
+        raise RuntimeError(f'Attention.{flag} is an evaluation-time switch: the observed attention path has no backward. '
+                           f'Run the model under torch.no_grad() (and in eval mode), or clear {flag}.')
+    window = tuple(window)
+    x = x.contiguous()
+    h, _mean, _rstd = _pre(x, nw, nb, mode, eps)
+    if lengths is not None:
+        if h is x: h = h.clone()
+        ops.mask_rows_(h, lengths, B, N)
+    wqh, woh = wcast(wqkv, regroup=True), wcast(wout)
+    bq = None if bqkv is None else _regrouped(bqkv.detach().view(-1, 1)).view(-1).contiguous()
+    if cos is not None:
+        qkv = ops.gemm_qkv_rotary(h, wqh, bq, cos, sin, N, H, D)
+    else:
+        qkv = ops.gemm(h, wqh, 'nt', bias=bq)
+    q5 = qkv.view(B, N, 3, H, D)
+    o, lse = ops.attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], lengths, window)
+    y = ops.gemm(o.view(B * N, H * D), woh, 'nt', bias=bout, resid=x if residual else None, out_dtype=F32)
+    observer(q5[:, :, 0], q5[:, :, 1], lse, lengths, window)
+    return y
+
+
 # =================================================================================================
 # x + ConformerConvolution(norm(x))  — PreNorm(ConformerConvolution) with BatchRenorm1d; convolution.py:103-124
 # =================================================================================================

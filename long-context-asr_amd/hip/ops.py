@@ -411,6 +411,40 @@ def attn_bwd(q, k, v, o, dout, lse, lengths, window=(-1, -1), scale: Optional[fl
     return dq, dk, dv
 
 
+def attn_scores(q: torch.Tensor, k: torch.Tensor, lengths: Optional[torch.Tensor], window=(-1, -1), scale: Optional[float] = None,
+                out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """q,k (B,N,H,D) bf16 (may be strided views) -> scaled scores (B,H,N,N) f32 or bf16, -inf at masked positions (key or query row
+    past `lengths`, key outside the window)."""
+    B, N, H, D = q.shape
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16: raise TypeError('attn_scores: q and k must be bfloat16')
+    if tuple(k.shape) != (B, N, H, D): raise ValueError('attn_scores: q and k must have the same (B,N,H,D) shape')
+    if lengths is not None: _chk(lengths, 'lengths', torch.int32)
+    out = torch.empty(B, H, N, N, dtype=out_dtype, device=q.device)
+    sc = float(scale) if scale is not None else D ** -0.5
+    _lib.call('sconf_attn_scores', _p(q), _p(k), _p(out), _dt(out), _p(lengths), B, N, H, D, _strides3(q), _strides3(k),
+              int(window[0]), int(window[1]), sc, _stream())
+    return out
+
+
+def attn_offset_profile(q: torch.Tensor, k: torch.Tensor, lse: torch.Tensor, lengths: Optional[torch.Tensor], window=(-1, -1),
+                        scale: Optional[float] = None) -> torch.Tensor:
+    """-> (B,H,2N-1) f32: entry delta + N - 1 is the attention probability summed along the diagonal j - i = delta, with
+    P = exp(scale q.k - lse) and lse (B,H,N) f32 from attn_fwd on the same operands, lengths and window.  Fixed summation order."""
+    B, N, H, D = q.shape
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16: raise TypeError('attn_offset_profile: q and k must be bfloat16')
+    if tuple(k.shape) != (B, N, H, D): raise ValueError('attn_offset_profile: q and k must have the same (B,N,H,D) shape')
+    _chk(lse, 'lse', torch.float32)
+    if tuple(lse.shape) != (B, H, N): raise ValueError('attn_offset_profile: lse must be (B,H,N)')
+    if lengths is not None: _chk(lengths, 'lengths', torch.int32)
+    prof = torch.empty(B, H, 2 * N - 1, dtype=torch.float32, device=q.device)
+    nws = int(_lib.load().sconf_attn_offset_profile_workspace(B, N, H, int(window[0]), int(window[1])))
+    ws = _workspace(nws, q.device)
+    sc = float(scale) if scale is not None else D ** -0.5
+    _lib.call('sconf_attn_offset_profile', _p(q), _p(k), _p(lse), _p(prof), _p(lengths), B, N, H, D, _strides3(q), _strides3(k),
+              int(window[0]), int(window[1]), sc, _p(ws), nws, _stream())
+    return prof
+
+
 # ------------------------------------------------------------------------------------------------
 # conformer conv module
 # ------------------------------------------------------------------------------------------------
