@@ -6,9 +6,6 @@
 #include "common.h"
 #include <algorithm>
 
-// csrc/infer.hip: frame arg-maxes, first index on ties - the pseudo-labels must break ties as the greedy decoder does
-SCONF_API int sconf_argmax_rows(const float* x, int64_t M, int64_t C, int32_t* idx, hipStream_t stream);
-
 namespace {
 
 constexpr int MASK_CHUNK = 4096;      // elements of one (b, f) row per workgroup: 4 x 16 B per thread

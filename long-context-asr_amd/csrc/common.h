@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include "../../include/sconf.h"   // the public C ABI: every SCONF_API definition is compiled against its declaration
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -20,12 +21,16 @@ int sconf_set_error(const char* fmt, ...);
 #define SCONF_LAUNCH_OK(name) do { hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) return sconf_set_error("%s: launch failed: %s", name, hipGetErrorString(e_)); } while (0)
 
-enum SconfDtype { SCONF_F32 = 0, SCONF_BF16 = 1 };
-enum SconfAct { SCONF_ACT_NONE = 0, SCONF_ACT_GELU = 1, SCONF_ACT_SILU = 2, SCONF_ACT_DGELU = 3, SCONF_ACT_DSILU = 4,
-                SCONF_ACT_GELU_DSAVE = 5,   // out = gelu(v); `pre` receives gelu'(v) (what the backward multiplies by)
-                SCONF_ACT_MULAUX = 6,       // out = v * aux
-                SCONF_ACT_SMAXBWD = 7 };    // out = (v - rowv[m]) * aux (softmax backward; sconf_gemm_softmax_bwd only)
-
+// ---- library-private functions called across files (defined in subsample_mfma.hip, called from subsample.hip) --------
+// conv0 on the matrix cores; the launchers return 1 when they took the problem
+int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const float* b0, const float* wd, const float* bd, void* d1,
+                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
+int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
+                           float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
+int sconf_dwconv_window_fwd(const void* x, const float* w, const float* bias, void* y, int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream);
+int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
+int stage01_mfma_slabs(int64_t F, int64_t C, int bwd);
 
 // ---- device helpers --------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }

@@ -553,10 +553,6 @@ __global__ __launch_bounds__(256) void ctc_grad_logits_kernel(const float* __res
 
 }  // namespace
 
-SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
-                           int64_t workspace_bytes, hipStream_t stream);
-SCONF_API int64_t sconf_colsum_workspace(int64_t M, int64_t N);
-
 // Workspace contract: lpg, alpha, beta are f32 [B][N][Lmax] with Lmax = 2*Smax+1 (caller-allocated); offs is f64 [2*B*N + B]:
 // the per-frame offsets of the renormalised alpha rows, of the beta rows, and the nll in f64 (read back by the backward).
 // targets int32 [B][Smax]; input_lengths / target_lengths int32 [B].  nll f32 [B] (loss = sum).
@@ -625,7 +621,6 @@ SCONF_API int sconf_ctc_fwd_logits(const float* logits, const int32_t* targets, 
     return 0;
 }
 
-SCONF_API int sconf_num_cus(void);
 static int ctc_bwd_slabs() {                            // workgroups of the fused gradient kernel (each keeps a slab of column sums)
     static int v = 0;
     if (!v) { const char* e = getenv("SCONF_CTC_BWD_SLABS"); v = e ? atoi(e) : 0; if (v < 64 || v > 65536) { const int n = sconf_num_cus(); v = 12 * (n > 0 ? n : 256); } }   // 6 resident per CU: whole rounds (2048: 2.78 ms, 3072: 2.63 at B = 128)

@@ -425,9 +425,6 @@ SCONF_API int sconf_rowdot(const void* a, const void* b, const float* bias, floa
     return 0;
 }
 
-SCONF_API int sconf_colsum(const void* x, int x_dtype, float* out, int64_t M, int64_t N, int64_t ld, float alpha, void* workspace,
-                           int64_t workspace_bytes, hipStream_t stream);
-SCONF_API int64_t sconf_colsum_workspace(int64_t M, int64_t N);
 // floats of scratch sconf_softmax_bwd needs when it also produces the column sums of dx: the slabs, then the column sum's workspace
 SCONF_API int64_t sconf_softmax_bwd_workspace(int64_t M, int64_t C) {
     const long slabs = std::min<long>(M, SOFTMAX_BWD_SLABS);

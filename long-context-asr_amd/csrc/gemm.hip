@@ -21,8 +21,6 @@
 #include <stdlib.h>
 #include <algorithm>
 
-SCONF_API int sconf_num_cus(void);
-
 namespace {
 using namespace gemm_tile;
 
@@ -384,8 +382,6 @@ SCONF_API int sconf_gemm_bf16(int layout, const void* A, const void* B, void* C,
         return rc < 0 ? 0 : rc;
     return gemm_launch(p, layout, stream);
 }
-
-SCONF_API int sconf_rotary_inplace(void* qkv, const float* cos_tab, const float* sin_tab, int64_t B, int64_t N, int64_t H, int64_t D, hipStream_t stream);
 
 // qkv projection with the rotary rotation in the GEMM epilogue: C (M, 3, H, D) bf16 = [q | k | v] = x W^T (+ bias) with W in the
 // REGROUPED row order (sconf_cast_shadows, R < 0) and q, k rotated by the NeoX rotary of position (row % seq_len) - attention.py:485,

@@ -30,8 +30,6 @@
 #include <stdlib.h>
 #include <stdio.h>
 
-SCONF_API int sconf_num_cus(void);
-
 namespace {
 using namespace gemm_tile;
 

@@ -12,8 +12,6 @@
 #include "common.h"
 #include <stdlib.h>
 
-SCONF_API int sconf_num_cus(void);
-
 namespace {
 
 constexpr int MAXD = 2048;                   // d <= 8 * 256; kernels are instantiated for NIT = ceil(d/256) in {1,2,3,4,8}

@@ -540,17 +540,6 @@ __global__ __launch_bounds__(256) void stage01_bwd_kernel(const TX* __restrict__
     fused_reduce<1>(gbd, g, C, red, dbd, 1);
 }
 
-}  // namespace
-// subsample_mfma.hip: conv0 on the matrix cores; return 1 when they took the problem
-int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const float* b0, const float* wd, const float* bd, void* d1,
-                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
-int sconf_dwconv_window_fwd(const void* x, const float* w, const float* bias, void* y, int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream);
-int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
-                           float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
-                           int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream);
-int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C);
-int stage01_mfma_slabs(int64_t F, int64_t C, int bwd);
-namespace {
 
 struct LaunchGeo { int PL, iters, threads; dim3 grid; };
 // npos positions per batch item; aim for ~target workgroups in total.

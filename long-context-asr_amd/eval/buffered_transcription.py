@@ -15,6 +15,7 @@ from typing import List, Tuple
 import torch
 
 from .. import functional as Fn          # Fn.ops: the HIP op layer (tests swap it for the CPU kernel references)
+from .utils import resolve_windowing
 
 
 def buffer_plan(spec_n: int, seq_len: int, overlap: int) -> List[Tuple[int, int, int, int]]:
@@ -83,14 +84,7 @@ def fetch_logits(args, model, spec: torch.Tensor, seq_len: int, overlap: int, to
     if spec.dim() != 3 or spec.shape[0] != 1:
         raise ValueError(f'spec must be (1, features, time), got {tuple(spec.shape)}')
     spec_n = spec.shape[-1]
-    downsampling_factor = model.subsampling.subsampling_factor
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
-    if seq_len > spec_n:
-        seq_len = spec_n
-        overlap = 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
-    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    seq_len, overlap = resolve_windowing(args, spec_n, seq_len, overlap, model.subsampling.subsampling_factor)
 
     what = f'buffer_plan(spec_n={spec_n}, seq_len={seq_len}, overlap={overlap})'
     plan = buffer_plan(spec_n, seq_len, overlap)

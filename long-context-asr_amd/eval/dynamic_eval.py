@@ -30,7 +30,7 @@ from .. import functional as Fn          # Fn.ops: the HIP op layer (tests swap 
 from ..decoding.greedy import GreedyCTCDecoder
 from ..optim import MADGRAD
 from ..utils.augmentation import SpecAugment
-from .utils import window_plan
+from .utils import resolve_windowing, window_plan
 
 DEFAULT_SPEC_AUGMENT = {'n_time_masks': 2, 'n_freq_masks': 3, 'freq_mask_param': 42, 'time_mask_param': -1, 'min_p': 0.05,
                         'zero_masking': False}
@@ -46,13 +46,8 @@ def dynamic_eval_ctc_loss(args, model, spec: torch.Tensor, seq_len: int, overlap
         raise ValueError(f'spec must be (1, features, time), got {tuple(spec.shape)}')
     spec_n = spec.shape[-1]
     downsampling_factor = args.config.get('model', {}).get('subsampling_factor', model.subsampling.subsampling_factor)   # :33
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']                                          # :34
-    if seq_len > spec_n:                                                                                                   # :52-55
-        seq_len, overlap = spec_n, 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
     assert args.config.get('training', {}).get('max_seq_len', 0) == 0, 'caching is not used anymore'                      # :57
-    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'   # :58
+    seq_len, overlap = resolve_windowing(args, spec_n, seq_len, overlap, downsampling_factor)                             # :34, :52-55, :58
 
     dev = next(model.parameters()).device
     blank = model.decoder.num_classes - 1

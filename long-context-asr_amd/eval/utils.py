@@ -29,6 +29,18 @@ def window_plan(spec_n: int, seq_len: int, overlap: int) -> List[Tuple[int, int]
     return plan
 
 
+def resolve_windowing(args, spec_n: int, seq_len: int, overlap: int, downsampling_factor: int) -> Tuple[int, int]:
+    """(seq_len, overlap) as every evaluation loop of the reference resolves them (utils.py:59-68): -1 means the value of
+    args.config['audio_chunking'], a window longer than the recording becomes the whole recording without overlap."""
+    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
+    if seq_len > spec_n:
+        seq_len, overlap = spec_n, 0
+    else:
+        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
+    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    return seq_len, overlap
+
+
 @torch.no_grad()
 def fetch_logits(args, model, spec: torch.Tensor, seq_len: int, overlap: int, tokenizer, use_tqdm=True, batched: bool = True,
                  max_batch: int = 16, return_numpy: bool = True):
@@ -39,14 +51,7 @@ def fetch_logits(args, model, spec: torch.Tensor, seq_len: int, overlap: int, to
     if spec.dim() != 3 or spec.shape[0] != 1:
         raise ValueError(f'spec must be (1, features, time), got {tuple(spec.shape)}')
     spec_n = spec.shape[-1]
-    downsampling_factor = model.subsampling.subsampling_factor
-    seq_len = seq_len if seq_len != -1 else args.config['audio_chunking']['size']
-    if seq_len > spec_n:
-        seq_len = spec_n
-        overlap = 0
-    else:
-        overlap = overlap if overlap != -1 else args.config['audio_chunking']['overlap']
-    assert overlap / downsampling_factor == overlap // downsampling_factor, 'Overlap must be a multiple of the downsampling factor'
+    seq_len, overlap = resolve_windowing(args, spec_n, seq_len, overlap, model.subsampling.subsampling_factor)
 
     dev = next(model.parameters()).device
     C = tokenizer.vocab_size() + 1

@@ -113,32 +113,29 @@ def _regrouped(w2: torch.Tensor) -> torch.Tensor:
     return w2.view(R // 3, 3, C).permute(1, 0, 2).reshape(R, C)
 
 
+def _cast_slot(w: torch.Tensor, regroup: bool, slot: str, ver: str, cast) -> torch.Tensor:
+    """The shadow of w kept in `slot` ('n' / 't', cast state in `ver`), made by cast(2-D master, rows regrouped on request)."""
+    e = _shadow(w, regroup)
+    st = _state(e)
+    if getattr(e, slot) is None or getattr(e, ver) != st:   # first use / the master changed since the last cast (module-level use after an update)
+        src = w.detach().reshape(e.rows, e.cols)
+        fresh = cast(_regrouped(src) if regroup else src)
+        if getattr(e, slot) is None: setattr(e, slot, fresh)   # refreshed in bulk from the next forward on
+        else: getattr(e, slot).copy_(fresh)
+    setattr(e, ver, st)
+    return getattr(e, slot)
+
+
 def wcast(w: torch.Tensor, regroup: bool = False) -> torch.Tensor:
     """bf16 copy of an f32 master weight, viewed 2-D (out_features, in_features*k).  regroup: the fused qkv projection's rows
     "(h d qkv)" come out as [q | k | v], so its GEMM writes three contiguous (h, d) blocks per token."""
-    e = _shadow(w, regroup)
-    st = _state(e)
-    if e.n is None or e.vn != st:                    # first use / the master changed since the last cast (module-level use after an update)
-        src = w.detach().reshape(e.rows, e.cols)
-        fresh = ops.cast(_regrouped(src).contiguous() if regroup else src, BF16)
-        if e.n is None: e.n = fresh                  # refreshed in bulk from the next forward on
-        else: e.n.copy_(fresh)
-    e.vn = st
-    return e.n
+    return _cast_slot(w, regroup, 'n', 'vn', lambda src: ops.cast(src.contiguous() if regroup else src, BF16))
 
 
 def wcast_t(w: torch.Tensor, regroup: bool = False) -> torch.Tensor:
     """Transposed bf16 copy (in_features*k, out_features) of an f32 master weight: dgrad dx = dy W becomes the NT GEMM
     dy (W^T)^T whose B operand is K-contiguous (wide epilogue, no transposed LDS reads).  Weights are a few MB."""
-    e = _shadow(w, regroup)
-    st = _state(e)
-    if e.t is None or e.vt != st:
-        src = w.detach().reshape(e.rows, e.cols)
-        fresh = ops.cast_transpose((_regrouped(src) if regroup else src).contiguous())
-        if e.t is None: e.t = fresh
-        else: e.t.copy_(fresh)
-    e.vt = st
-    return e.t
+    return _cast_slot(w, regroup, 't', 'vt', lambda src: ops.cast_transpose(src.contiguous()))
 
 
 # ---- parameter gradients ---------------------------------------------------------------------------------------------
@@ -380,6 +377,25 @@ def ff_block(x, nw, nb, w1, w2, b1, b2, scale=0.5, mode='layer_norm', eps=1e-5, 
 # =================================================================================================
 # x + out_proj(Attention(rotary(qkv(norm(x)))))  — PreNorm(Attention); attention.py:509-551
 # =================================================================================================
+def _attn_fwd(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, window, mode, eps, residual):
+    """The forward kernels of the attention block -> (y, x contiguous, h, mean, rstd, qkv (M, 3 H D) post-rotary, o, lse)."""
+    x = x.contiguous()
+    h, mean, rstd = _pre(x, nw, nb, mode, eps)
+    if lengths is not None:
+        if h is x: h = h.clone()
+        ops.mask_rows_(h, lengths, B, N)                                              # attention.py:511
+    wqh, woh = wcast(wqkv, regroup=True), wcast(wout)
+    bq = None if bqkv is None else _regrouped(bqkv.detach().view(-1, 1)).view(-1).contiguous()
+    if cos is not None:                                                               # rotation in the GEMM epilogue (head_dim 128), else in place
+        qkv = ops.gemm_qkv_rotary(h, wqh, bq, cos, sin, N, H, D)                      # (M, 3*H*D) = (B, N, 3, H, D)
+    else:
+        qkv = ops.gemm(h, wqh, 'nt', bias=bq)
+    q5 = qkv.view(B, N, 3, H, D)
+    o, lse = ops.attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], lengths, window)     # padded query rows come back zero
+    y = ops.gemm(o.view(B * N, H * D), woh, 'nt', bias=bout, resid=x if residual else None, out_dtype=F32)
+    return y, x, h, mean, rstd, qkv, o, lse
+
+
 class AttnBlockFn(Function):
     """The qkv projection reads a REGROUPED bf16 shadow of its weight (rows [q | k | v] instead of the reference's "(h d qkv)"
     interleave), so its GEMM writes (M, 3, H, D) and q, k, v are strided views of that one buffer: no de-interleave pass.
@@ -390,20 +406,8 @@ class AttnBlockFn(Function):
     @staticmethod
     def forward(ctx, x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B: int, N: int, H: int, D: int, window,
                 mode: str, eps: float, residual: bool):
-        x = x.contiguous()
-        h, mean, rstd = _pre(x, nw, nb, mode, eps)
-        if lengths is not None:
-            if h is x: h = h.clone()
-            ops.mask_rows_(h, lengths, B, N)                                          # attention.py:511
-        wqh, woh = wcast(wqkv, regroup=True), wcast(wout)
-        bq = None if bqkv is None else _regrouped(bqkv.detach().view(-1, 1)).view(-1).contiguous()
-        if cos is not None:                                                           # rotation in the GEMM epilogue (head_dim 128), else in place
-            qkv = ops.gemm_qkv_rotary(h, wqh, bq, cos, sin, N, H, D)                  # (M, 3*H*D) = (B, N, 3, H, D)
-        else:
-            qkv = ops.gemm(h, wqh, 'nt', bias=bq)
-        q5 = qkv.view(B, N, 3, H, D)
-        o, lse = ops.attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], lengths, window)  # padded query rows come back zero
-        y = ops.gemm(o.view(B * N, H * D), woh, 'nt', bias=bout, resid=x if residual else None, out_dtype=F32)
+        y, x, h, mean, rstd, qkv, o, lse = _attn_fwd(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, window,
+                                                     mode, eps, residual)
         ctx.save_for_backward(x, nw, nb, mean, rstd, wcast_t(wqkv, regroup=True), wcast_t(wout), bqkv, bout, cos, sin, lengths, h, qkv, o, lse)
         ctx.cfg = (B, N, H, D, window, mode, eps, residual)
         ctx.P = (nw, nb, wqkv, wout, bqkv, bout)
@@ -454,28 +458,17 @@ def attn_block(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D,
 
 
 def attn_block_observed(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, window, mode, eps, residual, observer, flag):
-    """The attention block with an observer (Attention.return_attention_weights / return_attention_offsets): the kernel sequence
-    of AttnBlockFn.forward outside autograd, then observer(q, k, lse, lengths, window) on the post-rotary q and k blocks of the
+    """The attention block with an observer (Attention.return_attention_weights / return_attention_offsets): the forward kernels
+    of AttnBlockFn (_attn_fwd) outside autograd, then observer(q, k, lse, lengths, window) on the post-rotary q and k blocks of the
     qkv buffer and the forward's row log-sum-exp.  The result is bit-equal to attn_block's.  Analysis only: there is no backward,
     so it refuses to run where one would be recorded.  `flag` names the switch in the error."""
     if torch.is_grad_enabled():
         raise RuntimeError(f'Attention.{flag} is an evaluation-time switch: the observed attention path has no backward. '
                            f'Run the model under torch.no_grad() (and in eval mode), or clear {flag}.')
     window = tuple(window)
-    x = x.contiguous()
-    h, _mean, _rstd = _pre(x, nw, nb, mode, eps)
-    if lengths is not None:
-        if h is x: h = h.clone()
-        ops.mask_rows_(h, lengths, B, N)
-    wqh, woh = wcast(wqkv, regroup=True), wcast(wout)
-    bq = None if bqkv is None else _regrouped(bqkv.detach().view(-1, 1)).view(-1).contiguous()
-    if cos is not None:
-        qkv = ops.gemm_qkv_rotary(h, wqh, bq, cos, sin, N, H, D)
-    else:
-        qkv = ops.gemm(h, wqh, 'nt', bias=bq)
+    y, _x, _h, _mean, _rstd, qkv, _o, lse = _attn_fwd(x, nw, nb, wqkv, wout, bqkv, bout, cos, sin, lengths, B, N, H, D, window,
+                                                      mode, eps, residual)
     q5 = qkv.view(B, N, 3, H, D)
-    o, lse = ops.attn_fwd(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], lengths, window)
-    y = ops.gemm(o.view(B * N, H * D), woh, 'nt', bias=bout, resid=x if residual else None, out_dtype=F32)
     observer(q5[:, :, 0], q5[:, :, 1], lse, lengths, window)
     return y
 
@@ -604,23 +597,41 @@ def selfcond_block(x, nw, nb, wff, bff, wre, bre, has_norm=True, mode='layer_nor
 # =================================================================================================
 # decoder head: [norm] -> norm -> Linear -> log_softmax   — sconformer_xl.py:246-247, decoder.py:22-26
 # =================================================================================================
+def _head_norm_fwd(x, hn_pre, nw, nb, n_norms: int, mode: str, eps: float):
+    """The decoder norm(s) in front of the head's Linear -> (hn bf16, n_norms, tensors the backward needs).  hn_pre: the norms were
+    applied by the producer of x (n_norms comes back as -1); otherwise 0, 1 or 2 norms run here."""
+    if hn_pre is not None:
+        return hn_pre.contiguous(), -1, []
+    saved_norm = []
+    x = x.contiguous()
+    cur = x
+    for i in range(n_norms):                                                           # legacy double norm: applied twice
+        out_dt = BF16 if i == n_norms - 1 else F32
+        y, mean, rstd = ops.norm_fwd(cur, nw, nb, mode, eps, out_dt)
+        saved_norm += [cur, mean, rstd]
+        cur = y
+    return (cur if n_norms > 0 else ops.cast(x, BF16)), n_norms, saved_norm
+
+
+def _head_norm_bwd(g, sn, nw, pnw, pnb, n_norms: int, mode: str, eps: float):
+    """Backward of _head_norm_fwd from g = d loss / d hn (bf16): the gradients of (x, hn_pre, nw, nb)."""
+    if n_norms < 0:                                                                    # pre-normalised input: its producer applies the norms' backward
+        return None, g, None, None
+    dnw, dnb = _G(pnw if n_norms > 0 else None), _G(pnb if n_norms > 0 else None)
+    for i in reversed(range(n_norms)):
+        xin, mean, rstd = sn[3 * i:3 * i + 3]
+        g = ops.norm_bwd(g, xin, nw, mean, rstd, mode, eps, None, F32, dnw.t, dnb.t)
+    if n_norms == 0:
+        g = ops.cast(g, F32)
+    return g, None, dnw.out(), dnb.out()
+
+
 class HeadFn(Function):
     @staticmethod
     def forward(ctx, x, hn_pre, nw, nb, wff, bff, n_norms: int, mode: str, eps: float, return_logits: bool):
         """hn_pre (bf16, optional): the decoder norm(s) of x already applied by the producer of x (Norm2Fn) - x is then unused here
         and the gradient of hn_pre goes back to the producer."""
-        saved_norm = []
-        if hn_pre is not None:
-            hn, n_norms = hn_pre.contiguous(), -1
-        else:
-            x = x.contiguous()
-            cur = x
-            for i in range(n_norms):                                                   # legacy double norm: applied twice
-                out_dt = BF16 if i == n_norms - 1 else F32
-                y, mean, rstd = ops.norm_fwd(cur, nw, nb, mode, eps, out_dt)
-                saved_norm += [cur, mean, rstd]
-                cur = y
-            hn = cur if n_norms > 0 else ops.cast(x, BF16)
+        hn, n_norms, saved_norm = _head_norm_fwd(x, hn_pre, nw, nb, n_norms, mode, eps)
         wfh = wcast(wff)
         logits = ops.gemm(hn, wfh, 'nt', bias=bff, out_dtype=F32)
         out = logits if return_logits else ops.softmax_fwd(logits, True, F32)
@@ -646,15 +657,7 @@ class HeadFn(Function):
             dbf = gbf.out()
         dwf = _wgrad(dl, hn, pwf)
         g = ops.gemm(dl, wft, 'nt')                                                    # (M,d) bf16
-        if n_norms < 0:                                                                # pre-normalised input: its producer applies the norms' backward
-            return None, g, None, None, dwf, dbf, None, None, None, None
-        dnw, dnb = _G(pnw if n_norms > 0 else None), _G(pnb if n_norms > 0 else None)
-        for i in reversed(range(n_norms)):
-            xin, mean, rstd = sn[3 * i:3 * i + 3]
-            g = ops.norm_bwd(g, xin, nw, mean, rstd, mode, eps, None, F32, dnw.t, dnb.t)
-        if n_norms == 0:
-            g = ops.cast(g, F32)
-        return g, None, dnw.out(), dnb.out(), dwf, dbf, None, None, None, None
+        return _head_norm_bwd(g, sn, nw, pnw, pnb, n_norms, mode, eps) + (dwf, dbf, None, None, None, None)
 
 
 def decoder_head(x, nw, nb, wff, bff, n_norms=1, mode='layer_norm', eps=1e-5, return_logits=False, prenormed=None):
@@ -674,18 +677,7 @@ class HeadCTCFn(Function):
 
     @staticmethod
     def forward(ctx, x, hn_pre, nw, nb, wff, bff, n_norms: int, mode: str, eps: float, B: int, targets, input_lengths, target_lengths, blank: int):
-        saved_norm = []
-        if hn_pre is not None:                                                         # as in HeadFn
-            hn, n_norms = hn_pre.contiguous(), -1
-        else:
-            x = x.contiguous()
-            cur = x
-            for i in range(n_norms):                                                   # legacy double norm: applied twice
-                out_dt = BF16 if i == n_norms - 1 else F32
-                y, mean, rstd = ops.norm_fwd(cur, nw, nb, mode, eps, out_dt)
-                saved_norm += [cur, mean, rstd]
-                cur = y
-            hn = cur if n_norms > 0 else ops.cast(x, BF16)
+        hn, n_norms, saved_norm = _head_norm_fwd(x, hn_pre, nw, nb, n_norms, mode, eps)
         logits = ops.gemm(hn, wcast(wff), 'nt', bias=bff, out_dtype=F32)               # (B N, V+1) f32
         lg3 = logits.view(B, -1, logits.shape[-1])
         nll, ws = ops.ctc_fwd_logits(lg3, targets, input_lengths, target_lengths, blank)
@@ -710,15 +702,7 @@ class HeadCTCFn(Function):
         dbf = gbf.out()
         dwf = _wgrad(dl, hn, pwf)
         g = ops.gemm(dl, wft, 'nt')                                                    # (M,d) bf16
-        if n_norms < 0:
-            return (None, g, None, None, dwf, dbf) + (None,) * 8
-        dnw, dnb = _G(pnw if n_norms > 0 else None), _G(pnb if n_norms > 0 else None)
-        for i in reversed(range(n_norms)):
-            xin, mean, rstd = sn[3 * i:3 * i + 3]
-            g = ops.norm_bwd(g, xin, nw, mean, rstd, mode, eps, None, F32, dnw.t, dnb.t)
-        if n_norms == 0:
-            g = ops.cast(g, F32)
-        return (g, None, dnw.out(), dnb.out(), dwf, dbf) + (None,) * 8
+        return _head_norm_bwd(g, sn, nw, pnw, pnb, n_norms, mode, eps) + (dwf, dbf) + (None,) * 8
 
 
 def decoder_head_ctc(x, nw, nb, wff, bff, B, targets, input_lengths, target_lengths, blank, n_norms=1, mode='layer_norm', eps=1e-5, prenormed=None,
@@ -727,57 +711,82 @@ def decoder_head_ctc(x, nw, nb, wff, bff, B, targets, input_lengths, target_leng
     num_labels: the number of real classes when wff carries padding rows (labels must stay below it)."""
     dev = x.device
     _check_ctc_host_args(targets, input_lengths, target_lengths, x.shape[0] // max(B, 1), wff.shape[0] if num_labels is None else num_labels)
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    il = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tg, il, tl = _ctc_int_args(dev, targets, input_lengths, target_lengths)
     return HeadCTCFn.apply(x, prenormed, nw, nb, wff, bff, n_norms, mode, eps, B, tg, il, tl, blank)
 
 
 # =================================================================================================
 # ConvSubsampling 'dw_striding' x8 and x4  — subsampling.py:276-321, 384-428
 # =================================================================================================
+def _sub_front(audio, w0f, b0, wd1f, bd1, wp1h, bp1):
+    """Fused stage 0 -> 1 and the first 1x1 conv -> (d1, pre1), both (B,T4,F4,C); stage 0 never hits HBM."""
+    d1 = ops.sub_stage01_fwd(audio, w0f, b0, wd1f, bd1)
+    return d1, ops.gemm(d1.view(-1, d1.shape[-1]), wp1h, 'nt', bias=bp1).view(d1.shape)
+
+
+def _sub_tail(pre, woh, bout):
+    """SiLU + transpose of the last 1x1 conv's output pre (B,N,Fk,C), then the output GEMM -> (s (B*N, C*Fk), x (B,N,d_model))."""
+    B, N, Fk, C = pre.shape
+    s = ops.sub_silu_transpose(pre.view(B * N, Fk, C))
+    return s, ops.gemm(s, woh, 'nt', bias=bout, out_dtype=F32).view(B, N, -1)
+
+
+def _sub_tail_bwd(dx, pre, s, wot, pwo, pbo):
+    """Backward of _sub_tail -> (dpre (B*N*Fk, C), dwout, dbout)."""
+    B, N, Fk, C = pre.shape
+    dx16 = ops.cast(dx.contiguous().view(B * N, -1), BF16)
+    ds = ops.gemm(dx16, wot, 'nt')                                                     # (B*N, C*Fk)
+    dwo = _wgrad(dx16, s, pwo)
+    dbo = _bgrad(dx16, pbo)
+    return ops.sub_silu_transpose(pre.view(B * N, Fk, C), ds).view(-1, C), dwo, dbo
+
+
+def _sub_pw_bwd(dpre, xin, wt, pw, pb, gb: Optional[_G] = None):
+    """Backward of a 1x1 conv pre = xin W^T + b from dpre (rows, C) -> (dW, db, dxin).  gb: the _G that already holds db, when the
+    producer of dpre took its column sums in the same pass; otherwise they are taken here."""
+    dw = _wgrad(dpre, xin.view(-1, xin.shape[-1]), pw)
+    db = _bgrad(dpre, pb) if gb is None else gb.out()
+    return dw, db, ops.gemm(dpre, wt, 'nt').view(xin.shape)
+
+
+def _sub_front_bwd(dpre1, gbp1, audio, w0f, b0, wd1f, wp1t, d1, pw0, pb0, pwd1, pbd1, pwp1, pbp1):
+    """Backward of _sub_front from dpre1 (rows, C) -> the gradients of (w0, b0, wd1, bd1, wp1, bp1); gbp1 as in _sub_pw_bwd."""
+    C = d1.shape[-1]
+    dwp1, dbp1, dd1 = _sub_pw_bwd(dpre1, d1, wp1t, pwp1, pbp1, gbp1)
+    dwd1, dbd1, dw0, db0 = _G(pwd1, (C, 9)), _G(pbd1), _G(pw0, (C, 9)), _G(pb0)
+    ops.sub_stage01_bwd_(dd1, audio, w0f, b0, wd1f, dw0.t, db0.t, dwd1.t, dbd1.t)      # conv0 recomputed; no (B,T/2,F/2,C) grads
+    return dw0.out(), db0.out(), dwd1.out(), dbd1.out(), dwp1, dbp1
+
+
 class SubsampleFn(Function):
+    """'dw_striding' x8: front, a second depthwise stage with its 1x1 conv, tail."""
+
     @staticmethod
     def forward(ctx, audio, w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout):
         audio = audio.contiguous()
-        B = audio.shape[0]
         C = w0.shape[0]
         w0f, wd1f, wd2f = (t.detach().reshape(C, 9).contiguous() for t in (w0, wd1, wd2))
         wp1h, wp2h, woh = wcast(wp1), wcast(wp2), wcast(wout)
-        d1 = ops.sub_stage01_fwd(audio, w0f, b0, wd1f, bd1)                            # (B,T4,F4,C); stage 0 never hits HBM
-        pre1 = ops.gemm(d1.view(-1, C), wp1h, 'nt', bias=bp1).view(d1.shape)
+        d1, pre1 = _sub_front(audio, w0f, b0, wd1f, bd1, wp1h, bp1)
         d2 = ops.sub_dwconv_fwd(pre1, wd2f, bd2)                                       # (B,N,F8,C)
         pre2 = ops.gemm(d2.view(-1, C), wp2h, 'nt', bias=bp2).view(d2.shape)
-        N, F8 = d2.shape[1], d2.shape[2]
-        s = ops.sub_silu_transpose(pre2.view(B * N, F8, C))                            # (B*N, C*F8)
-        x = ops.gemm(s, woh, 'nt', bias=bout, out_dtype=F32)
+        s, x = _sub_tail(pre2, woh, bout)
         ctx.save_for_backward(audio, w0f, wd1f, wd2f, wcast_t(wp1), wcast_t(wp2), wcast_t(wout), bp1, bp2, bout, b0, d1, pre1, d2, pre2, s)
         ctx.P = (w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout)
-        return x.view(B, N, -1)
+        return x
 
     @staticmethod
     def backward(ctx, dx):
         pw0, pb0, pwd1, pbd1, pwp1, pbp1, pwd2, pbd2, pwp2, pbp2, pwo, pbo = ctx.P
         audio, w0f, wd1f, wd2f, wp1t, wp2t, wot, bp1, bp2, bout, b0, d1, pre1, d2, pre2, s = ctx.saved_tensors
-        B, N, F8, C = d2.shape
-        dev = dx.device
-        dx16 = ops.cast(dx.contiguous().view(B * N, -1), BF16)
-        ds = ops.gemm(dx16, wot, 'nt')                                                 # (B*N, C*F8)
-        dwo = _wgrad(dx16, s, pwo)
-        dbo = _bgrad(dx16, pbo)
-        dpre2 = ops.sub_silu_transpose(pre2.view(B * N, F8, C), ds).view(-1, C)
-        dwp2 = _wgrad(dpre2, d2.view(-1, C), pwp2)
-        dbp2 = _bgrad(dpre2, pbp2)
-        dd2 = ops.gemm(dpre2, wp2t, 'nt').view(d2.shape)
+        C = d2.shape[-1]
+        dpre2, dwo, dbo = _sub_tail_bwd(dx, pre2, s, wot, pwo, pbo)
+        dwp2, dbp2, dd2 = _sub_pw_bwd(dpre2, d2, wp2t, pwp2, pbp2)
         dwd2, dbd2 = _G(pwd2, (C, 9)), _G(pbd2)
         gbp1 = _G(pbp1)                                                                # its bias gradient = column sums of dpre1: same pass
         dpre1 = ops.sub_dwconv_bwd(dd2, wd2f, pre1, dwd2.t, dbd2.t, colsum_into=gbp1.t).view(-1, C)
-        dwp1 = _wgrad(dpre1, d1.view(-1, C), pwp1)
-        dbp1 = gbp1.out()
-        dd1 = ops.gemm(dpre1, wp1t, 'nt').view(d1.shape)
-        dwd1, dbd1, dw0, db0 = _G(pwd1, (C, 9)), _G(pbd1), _G(pw0, (C, 9)), _G(pb0)
-        ops.sub_stage01_bwd_(dd1, audio, w0f, b0, wd1f, dw0.t, db0.t, dwd1.t, dbd1.t)  # conv0 recomputed; no (B,T/2,F/2,C) grads
-        return (None, dw0.out(), db0.out(), dwd1.out(), dbd1.out(), dwp1, dbp1, dwd2.out(), dbd2.out(), dwp2, dbp2, dwo, dbo)
+        front = _sub_front_bwd(dpre1, gbp1, audio, w0f, b0, wd1f, wp1t, d1, pw0, pb0, pwd1, pbd1, pwp1, pbp1)
+        return (None,) + front + (dwd2.out(), dbd2.out(), dwp2, dbp2, dwo, dbo)
 
 
 def subsample(audio, w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout):
@@ -785,41 +794,28 @@ def subsample(audio, w0, b0, wd1, bd1, wp1, bp1, wd2, bd2, wp2, bp2, wout, bout)
 
 
 class Subsample4Fn(Function):
-    """'dw_striding' x4 (two stride-2 stages, conv.{0,2,3}): the x8 chain cut after the first 1x1 conv - the fused stage 0 -> 1, the 1x1
-    GEMM, SiLU + transpose over the F/4 bins, the output GEMM."""
+    """'dw_striding' x4 (two stride-2 stages, conv.{0,2,3}): the x8 chain cut after the first 1x1 conv - front, then the tail over the
+    F/4 bins."""
 
     @staticmethod
     def forward(ctx, audio, w0, b0, wd1, bd1, wp1, bp1, wout, bout):
         audio = audio.contiguous()
-        B = audio.shape[0]
         C = w0.shape[0]
         w0f, wd1f = (t.detach().reshape(C, 9).contiguous() for t in (w0, wd1))
         wp1h, woh = wcast(wp1), wcast(wout)
-        d1 = ops.sub_stage01_fwd(audio, w0f, b0, wd1f, bd1)                            # (B,N,F4,C); stage 0 never hits HBM
-        pre1 = ops.gemm(d1.view(-1, C), wp1h, 'nt', bias=bp1).view(d1.shape)
-        N, F4 = d1.shape[1], d1.shape[2]
-        s = ops.sub_silu_transpose(pre1.view(B * N, F4, C))                            # (B*N, C*F4)
-        x = ops.gemm(s, woh, 'nt', bias=bout, out_dtype=F32)
+        d1, pre1 = _sub_front(audio, w0f, b0, wd1f, bd1, wp1h, bp1)
+        s, x = _sub_tail(pre1, woh, bout)
         ctx.save_for_backward(audio, w0f, wd1f, wcast_t(wp1), wcast_t(wout), b0, d1, pre1, s)
         ctx.P = (w0, b0, wd1, bd1, wp1, bp1, wout, bout)
-        return x.view(B, N, -1)
+        return x
 
     @staticmethod
     def backward(ctx, dx):
         pw0, pb0, pwd1, pbd1, pwp1, pbp1, pwo, pbo = ctx.P
         audio, w0f, wd1f, wp1t, wot, b0, d1, pre1, s = ctx.saved_tensors
-        B, N, F4, C = d1.shape
-        dx16 = ops.cast(dx.contiguous().view(B * N, -1), BF16)
-        ds = ops.gemm(dx16, wot, 'nt')                                                 # (B*N, C*F4)
-        dwo = _wgrad(dx16, s, pwo)
-        dbo = _bgrad(dx16, pbo)
-        dpre1 = ops.sub_silu_transpose(pre1.view(B * N, F4, C), ds).view(-1, C)
-        dwp1 = _wgrad(dpre1, d1.view(-1, C), pwp1)
-        dbp1 = _bgrad(dpre1, pbp1)
-        dd1 = ops.gemm(dpre1, wp1t, 'nt').view(d1.shape)
-        dwd1, dbd1, dw0, db0 = _G(pwd1, (C, 9)), _G(pbd1), _G(pw0, (C, 9)), _G(pb0)
-        ops.sub_stage01_bwd_(dd1, audio, w0f, b0, wd1f, dw0.t, db0.t, dwd1.t, dbd1.t)  # conv0 recomputed; no (B,T/2,F/2,C) grads
-        return (None, dw0.out(), db0.out(), dwd1.out(), dbd1.out(), dwp1, dbp1, dwo, dbo)
+        dpre1, dwo, dbo = _sub_tail_bwd(dx, pre1, s, wot, pwo, pbo)
+        front = _sub_front_bwd(dpre1, None, audio, w0f, b0, wd1f, wp1t, d1, pw0, pb0, pwd1, pbd1, pwp1, pbp1)
+        return (None,) + front + (dwo, dbo)
 
 
 def subsample4(audio, w0, b0, wd1, bd1, wp1, bp1, wout, bout):
@@ -856,6 +852,11 @@ def _check_ctc_host_args(targets, input_lengths, target_lengths, N: int, C: int)
         raise ValueError(f'CTC: target labels must be in [0, {C})')
 
 
+def _ctc_int_args(dev, targets, input_lengths, target_lengths):
+    """The kernels' form of the three integer tensors: int32, contiguous, on dev."""
+    return tuple(t.to(device=dev, dtype=torch.int32).contiguous() for t in (targets, input_lengths, target_lengths))
+
+
 def ctc_nll(log_probs_bnc, targets, input_lengths, target_lengths, blank: int) -> torch.Tensor:
     """Per-sample negative log-likelihoods (B,) from batch-major (B,N,C) f32 log-probs.
     Arguments torch.nn.CTCLoss rejects (input_length > N, target_length > targets.shape[1], a label outside [0, C)) raise
@@ -866,7 +867,5 @@ def ctc_nll(log_probs_bnc, targets, input_lengths, target_lengths, blank: int) -
     _check_ctc_host_args(targets, input_lengths, target_lengths, _N, _C)
     if _C % 4:                                            # the kernels move 4 classes per access: pad with impossible classes (p = 0)
         log_probs_bnc = torch.nn.functional.pad(log_probs_bnc, (0, 4 - _C % 4), value=-1e30)
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    il = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    tg, il, tl = _ctc_int_args(dev, targets, input_lengths, target_lengths)
     return CTCFn.apply(log_probs_bnc, tg, il, tl, blank)

@@ -65,7 +65,33 @@ PROTOTYPES = {
     'sconf_madgrad_step': [vp, vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, f32, i64, vp, vp],
     'sconf_madgrad_advance': [vp, vp, f32, vp],
 }
-PLAIN = {'sconf_softmax_bwd_workspace': ([i64, i64], C.c_int64), 'sconf_gemm_variant': ([i32, i64, i64, i64, i64, i64, i32, i32, i32, i32], C.c_int), 'sconf_norm_bwd_workspace': ([i64, i64], C.c_int64), 'sconf_norm2_bwd_workspace': ([i64, i64], C.c_int64), 'sconf_ctc_bwd_logits_workspace': ([i64, i64], C.c_int64), 'sconf_colsum_workspace': ([i64, i64], C.c_int64), 'sconf_sumsq_workspace': ([i64], C.c_int64), 'sconf_mean_f32_workspace': ([i64], C.c_int64), 'sconf_glu_dwconv_fwd_workspace': ([i64, i64, i64], C.c_int64), 'sconf_convmod_bwd_workspace': ([i64, i64, i64, i64, i32], C.c_int64), 'sconf_sub_dwconv_bwd_workspace': ([i64, i64, i64, i64, i32], C.c_int64), 'sconf_sub_stage01_bwd_workspace': ([i64, i64, i64, i64], C.c_int64), 'sconf_sub_stage01_slabs': ([i64, i64, i32], C.c_int), 'sconf_convmod_tile_frames': ([i64, i64, i64], C.c_int), 'sconf_convmod_bwd_rows_per_thread': ([i64, i64, i64], C.c_int), 'sconf_attn_waves': ([i64, i64, i64], C.c_int), 'sconf_attn_offset_profile_workspace': ([i64, i64, i64, i32, i32], C.c_int64), 'sconf_edit_strip_cols': ([], C.c_int), 'sconf_edit_pass_cols': ([], C.c_int), 'sconf_edit_block_rows': ([], C.c_int), 'sconf_edit_counts_workspace': ([i64, i64, i64], C.c_int64), 'sconf_version': ([], C.c_int), 'sconf_num_cus': ([], C.c_int), 'sconf_last_error': ([], C.c_char_p)}
+# name -> (argtypes, restype): the entry points that return a value instead of a status
+PLAIN = {
+    'sconf_softmax_bwd_workspace': ([i64, i64], C.c_int64),
+    'sconf_gemm_variant': ([i32, i64, i64, i64, i64, i64, i32, i32, i32, i32], C.c_int),
+    'sconf_norm_bwd_workspace': ([i64, i64], C.c_int64),
+    'sconf_norm2_bwd_workspace': ([i64, i64], C.c_int64),
+    'sconf_ctc_bwd_logits_workspace': ([i64, i64], C.c_int64),
+    'sconf_colsum_workspace': ([i64, i64], C.c_int64),
+    'sconf_sumsq_workspace': ([i64], C.c_int64),
+    'sconf_mean_f32_workspace': ([i64], C.c_int64),
+    'sconf_glu_dwconv_fwd_workspace': ([i64, i64, i64], C.c_int64),
+    'sconf_convmod_bwd_workspace': ([i64, i64, i64, i64, i32], C.c_int64),
+    'sconf_sub_dwconv_bwd_workspace': ([i64, i64, i64, i64, i32], C.c_int64),
+    'sconf_sub_stage01_bwd_workspace': ([i64, i64, i64, i64], C.c_int64),
+    'sconf_sub_stage01_slabs': ([i64, i64, i32], C.c_int),
+    'sconf_convmod_tile_frames': ([i64, i64, i64], C.c_int),
+    'sconf_convmod_bwd_rows_per_thread': ([i64, i64, i64], C.c_int),
+    'sconf_attn_waves': ([i64, i64, i64], C.c_int),
+    'sconf_attn_offset_profile_workspace': ([i64, i64, i64, i32, i32], C.c_int64),
+    'sconf_edit_strip_cols': ([], C.c_int),
+    'sconf_edit_pass_cols': ([], C.c_int),
+    'sconf_edit_block_rows': ([], C.c_int),
+    'sconf_edit_counts_workspace': ([i64, i64, i64], C.c_int64),
+    'sconf_version': ([], C.c_int),
+    'sconf_num_cus': ([], C.c_int),
+    'sconf_last_error': ([], C.c_char_p),
+}
 
 
 def load():

@@ -589,19 +589,23 @@ def sub_silu_transpose(pre: torch.Tensor, ds: Optional[torch.Tensor] = None) -> 
 # ------------------------------------------------------------------------------------------------
 # CTC
 # ------------------------------------------------------------------------------------------------
+def _ctc_workspace(x: torch.Tensor, name: str, targets: torch.Tensor, input_lengths: torch.Tensor, target_lengths: torch.Tensor):
+    """Argument checks of a CTC forward over x (B,N,C) f32 and its outputs: lpg, alpha, beta (B,N,2 Smax + 1) f32, nll (B,) f32, offs f64."""
+    _chk(x, name, torch.float32); _chk(targets, 'targets', torch.int32)
+    _chk(input_lengths, 'input_lengths', torch.int32); _chk(target_lengths, 'target_lengths', torch.int32)
+    B, N, _ = x.shape
+    L = 2 * targets.shape[1] + 1
+    lpg, alpha, beta = (torch.empty(B, N, L, dtype=torch.float32, device=x.device) for _ in range(3))
+    nll = torch.empty(B, dtype=torch.float32, device=x.device)
+    offs = torch.empty(2 * B * N + B, dtype=torch.float64, device=x.device)     # per-frame offsets of the renormalised rows + nll in f64
+    return lpg, alpha, beta, nll, offs
+
+
 def ctc_fwd(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor, target_lengths: torch.Tensor, blank: int):
     """log_probs (B,N,C) f32; targets (B,Smax) int32; lengths int32 (B,).  Returns nll (B,) f32 and the workspace."""
-    _chk(log_probs, 'log_probs', torch.float32); _chk(targets, 'targets', torch.int32)
-    _chk(input_lengths, 'input_lengths', torch.int32); _chk(target_lengths, 'target_lengths', torch.int32)
+    lpg, alpha, beta, nll, offs = _ctc_workspace(log_probs, 'log_probs', targets, input_lengths, target_lengths)
     B, N, Cn = log_probs.shape
     Smax = targets.shape[1]
-    L = 2 * Smax + 1
-    dev = log_probs.device
-    lpg = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    beta = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    nll = torch.empty(B, dtype=torch.float32, device=dev)
-    offs = torch.empty(2 * B * N + B, dtype=torch.float64, device=dev)          # per-frame offsets of the renormalised rows + nll in f64
     _lib.call('sconf_ctc_fwd', _p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths), _p(lpg), _p(alpha), _p(beta),
               _p(offs), _p(nll), B, N, Cn, Smax, int(blank), _stream())
     return nll, (lpg, alpha, beta, offs)
@@ -610,18 +614,10 @@ def ctc_fwd(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths: torch
 def ctc_fwd_logits(logits: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor, target_lengths: torch.Tensor, blank: int):
     """CTC loss straight from the decoder's logits (B,N,C) f32 (log_softmax folded into the emission gather).
     Returns nll (B,) f32 and the workspace (lse (B,N), lpg, alpha, beta, offs) the backward needs."""
-    _chk(logits, 'logits', torch.float32); _chk(targets, 'targets', torch.int32)
-    _chk(input_lengths, 'input_lengths', torch.int32); _chk(target_lengths, 'target_lengths', torch.int32)
+    lpg, alpha, beta, nll, offs = _ctc_workspace(logits, 'logits', targets, input_lengths, target_lengths)
     B, N, Cn = logits.shape
     Smax = targets.shape[1]
-    L = 2 * Smax + 1
-    dev = logits.device
-    lse = torch.empty(B, N, dtype=torch.float32, device=dev)
-    lpg = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    beta = torch.empty(B, N, L, dtype=torch.float32, device=dev)
-    nll = torch.empty(B, dtype=torch.float32, device=dev)
-    offs = torch.empty(2 * B * N + B, dtype=torch.float64, device=dev)
+    lse = torch.empty(B, N, dtype=torch.float32, device=logits.device)
     _lib.call('sconf_ctc_fwd_logits', _p(logits), _p(targets), _p(input_lengths), _p(target_lengths), _p(lse), _p(lpg), _p(alpha),
               _p(beta), _p(offs), _p(nll), B, N, Cn, Smax, int(blank), _stream())
     return nll, (lse, lpg, alpha, beta, offs)
