@@ -16,8 +16,10 @@
 //    buffered, one barrier per tile.
 //  * Backward = two kernels (dK/dV with keys resident per wave; dQ with queries resident per wave):
 //    no atomics, bitwise reproducible, at the price of recomputing S and dP once more.
+#ifdef SCONF_ATTN_STAMP
+#define SCONF_STAMPS                 // gfx950.h: STAMP_DECL / STAMP are live in this file
+#endif
 #include "common.h"
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -42,17 +44,10 @@ struct AttnParams {
     unsigned long long* stamps;       // diagnostic builds only (-DSCONF_ATTN_STAMP): per (workgroup, wave) segment cycle sums
 };
 
-// In-kernel time stamps (cdna_hip_programming.md section 7): a DIAGNOSTIC build only (make EXTRA=-DSCONF_ATTN_STAMP); in the product
-// build the macros are empty and no stamp executes.  Segment sums are kept per wave and written once after the loop, to a buffer
-// nothing else reads.
+// In-kernel time stamps (gfx950.h), DIAGNOSTIC build only (make EXTRA=-DSCONF_ATTN_STAMP): per (workgroup, wave) segment sums to p.stamps.
 #ifdef SCONF_ATTN_STAMP
-#define STAMP_DECL(n) unsigned long long st_acc_[n] = {}, st_last_ = 0; { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_last_ = t_; }
-#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                      __builtin_amdgcn_sched_barrier(0); st_acc_[i] += t_ - st_last_; st_last_ = t_; } while (0)
 #define STAMP_OUT(n) do { if (p.stamps && (threadIdx.x & 63) == 0) for (int i_ = 0; i_ < (n); ++i_) p.stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + i_] = st_acc_[i_]; } while (0)
 #else
-#define STAMP_DECL(n)
-#define STAMP(i)
 #define STAMP_OUT(n)
 #endif
 
@@ -91,15 +86,13 @@ template <int D> __device__ __forceinline__ int tile_off(int row, int ch) {
     return row * (2 * D) + ((ch ^ swz<D>(row)) << 4);
 }
 
-// ---- LDS-DMA staging of a [ROWS][D] bf16 tile (global_load_lds_dwordx4): no staging VGPRs, no ds_write, no guards --
+// ---- LDS-DMA staging of a [ROWS][D] bf16 tile (the builtin form of gfx950.h's dma16_asm): no staging VGPRs, no ds_write, no guards --
 // LDS destination is linear (wave base + lane*16), so the tile_off swizzle is applied to the per-lane SOURCE chunk and
 // undone by the same XOR on the fragment reads.  Rows beyond the tensor are clamped to its last row: their scores are
 // masked (keys) or their LSE is +inf (queries), so the duplicated finite data never reaches an output.
 template <int D, int ROWS>
 __device__ __forceinline__ void glds_tile(const bf16* base, long sn, int row0, int nrows_valid, char* lds, int tid) {
     constexpr int CPR = D / 8, CHUNKS = ROWS * CPR, PER = (CHUNKS + 255) / 256;
-    typedef const __attribute__((address_space(1))) void* gptr;
-    typedef __attribute__((address_space(3))) void* lptr;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int c = tid + 256 * i;
@@ -111,31 +104,7 @@ __device__ __forceinline__ void glds_tile(const bf16* base, long sn, int row0, i
     }
 }
 
-// ---- LDS-DMA issued from inline asm ----------------------------------------------------------------------------------
-// hipcc cannot tell an LDS read from the destination of an in-flight global_load_lds issued through the builtin, so it puts
-// `s_waitcnt vmcnt(0)` in front of the first LDS read that follows one in program order: issued at the top of a stage, the next
-// stage's tile had to LAND before the current stage could be computed (60 % of the wave-cycles of the 8-wave dK/dV kernel were
-// parked there).  An asm statement is opaque to that bookkeeping: the 8-wave kernels below issue their DMA here, wait for it
-// themselves (`dma_wait_all` right before the barrier that publishes the stage) and leave every LDS READ to the compiler.
-// For that to work the loop must hold NO vector-memory operation the compiler knows of (the hardware counter is in order and
-// shared: any `s_waitcnt vmcnt(N)` it emits for a load of its own - a fragment loaded before the loop whose wait it sinks to the
-// first use, a spill reload, a per-stage statistics load - also waits for the DMA issued before it).
-// M0 carries the wave's LDS destination base and is compiler-reserved: saved and restored inside the statement.
-__device__ __forceinline__ void dma16_asm(const void* gsrc, unsigned lds_dst_wave_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_wave_base) : "memory");
-}
-__device__ __forceinline__ void dma4_asm(const void* gsrc, unsigned lds_dst_wave_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_wave_base) : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-// [ROWS][D] bf16 tile by asm DMA, NTHR threads; same swizzled image as glds_tile
+// [ROWS][D] bf16 tile by asm DMA (gfx950.h: dma16_asm, waited for with wait_vm<0>()), NTHR threads; same swizzled image as glds_tile
 // `lds` = byte address of the tile in LDS as a wave-uniform (scalar) value
 template <int D, int ROWS, int NTHR>
 __device__ __forceinline__ void dma_tile(const bf16* base, long sn, int row0, int nrows_valid, unsigned lds, int tid) {
@@ -151,21 +120,8 @@ __device__ __forceinline__ void dma_tile(const bf16* base, long sn, int row0, in
     }
 }
 
-// ---- LDS-DMA through a buffer descriptor, a whole tile per asm statement (round 3) -----------------------------------------------
-// In-kernel stamps of the 8-wave forward (DESIGN, round 3) showed the DMA ISSUE of dma_tile above on every wave's critical
-// path: 950 cycles per stage for waves 0-3 and 1950 for waves 4-7 (12-25 % of the kernel) - per 16-byte piece a 64-bit address
-// (row clamp, multiply by the row stride, swizzle) rebuilt on the VALU plus an M0 save / set / restore around it.  Here the
-// per-lane part of the address is ONE loop-invariant 32-bit offset (a piece is NTHR / 16 whole rows further down: the swizzle
-// depends on row & 15 only), the rest is scalar: `buffer_load_dwordx4 voff, srd, soff offen lds` with soff and M0 stepped by
-// s_add.  Rows past the tensor need no clamp: the descriptor's range check returns zeros for them (their keys are masked and
-// their query rows are never stored).  3 scalar instructions + the load per piece, M0 saved and restored once per tile.
-typedef __amdgpu_buffer_rsrc_t srd_t;
-__device__ __forceinline__ srd_t make_srd(const void* base, long nbytes) {
-    const unsigned long a = (unsigned long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned nb = __builtin_amdgcn_readfirstlane((unsigned)(nbytes > 0xffffffffL ? 0xffffffffL : nbytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long)hi << 32) | lo), 0, nb, 0x00020000);
-}
+// ---- LDS-DMA through a buffer descriptor (gfx950.h: make_srd, dma_pieces): a piece is NTHR / 16 whole rows further down (the swizzle
+// depends on row & 15 only); rows past the tensor read as zeros (their keys are masked and their query rows are never stored) ----
 // bytes of a (rows, D) bf16 view with row stride sn (elements) that start at its first row
 template <int D> __device__ __forceinline__ long view_bytes(int rows, long sn) { return rows > 0 ? ((long)(rows - 1) * sn + D) * 2 : 0; }
 // this lane's source byte offset inside one pass (NTHR / (D / 8) rows) of a [rows][D] tile: the tile_off swizzle on the source chunk
@@ -174,23 +130,6 @@ template <int D, int NTHR> __device__ __forceinline__ unsigned tile_voff(long sn
     static_assert((NTHR / CPR) % 16 == 0, "a pass must be whole groups of 16 rows (the swizzle period)");
     const int row = tid / CPR, pos = tid % CPR;
     return (unsigned)(row * sn * 2 + ((pos ^ swz<D>(row)) << 4));
-}
-// NP pieces of a tile: piece k reads srd base + soff + k * sstep + voff and lands at lds_wave_base + k * LSTEP + lane * 16
-#define SCONF_DMA_FIRST "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
-#define SCONF_DMA_NEXT  "s_add_u32 m0, m0, %6\n\ts_add_u32 %1, %1, %4\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
-#define SCONF_DMA_LAST  "s_mov_b32 m0, %0"
-template <int NP, int LSTEP> __device__ __forceinline__ void dma_pieces(srd_t srd, unsigned voff, unsigned soff, unsigned sstep, unsigned lds_wave_base) {
-    static_assert(NP == 2 || NP == 4 || NP == 8, "tiles of 2, 4 or 8 pieces per wave");
-    unsigned keep;
-    if constexpr (NP == 8)
-        asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
-    else if constexpr (NP == 4)
-        asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
-    else
-        asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_LAST
-                     : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
 }
 // A [ROWS][128] tile staged by a 512-thread workgroup = ROWS / 32 passes of 8 wave pieces.  Who issues them: every wave its own
 // piece of each pass, or - LOADERS - waves 0-3 only, each also the piece of wave w + 4 (16 rows further down: same swizzle, the
@@ -204,13 +143,6 @@ template <int ROWS, bool LOADERS> __device__ __forceinline__ void dma_tile128(sr
     if constexpr (!LOADERS) dma_pieces<PASSES, 8192>(srd, voff, (unsigned)row0 * rb, 32u * rb, lds_tile + (unsigned)wave_u * 1024u);
     else if (wave_u < 4) dma_pieces<2 * PASSES, 4096>(srd, voff, (unsigned)row0 * rb, 16u * rb, lds_tile + (unsigned)wave_u * 1024u);
 }
-
-// make a fragment array's loads complete, as far as the compiler can tell, HERE (an empty asm that "rewrites" each register)
-template <int NF> __device__ __forceinline__ void pin_frags(bf16x8 (&f)[NF]) {
-#pragma unroll
-    for (int i = 0; i < NF; ++i) asm volatile("" : "+v"(f[i]));
-}
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
 // Loop-invariant per-lane LDS byte offsets.  tile_off's swizzle depends only on (row & 3) and ((row >> 2) & 3), so a
 // row base that is a multiple of 16 adds linearly (rbase * 2D) and every fragment read is "lane offset + constant":
@@ -237,9 +169,8 @@ template <int D> __device__ __forceinline__ bf16x8 frag_row(const char* s, const
 // (tile_off: ((row >> 2) & 3) ^ 2), i.e. the byte offset is (trlo ^ 32) + 8 rows.  `x32` is that 32: callers short of registers
 // pass an opaque copy made inside their loop, so that hipcc cannot hoist the D/32 derived offsets back into live registers.
 template <int D> __device__ __forceinline__ bf16x8 frag_tr(const char* s, const LaneOffs<D>& L, int rb, int db, int x32 = 32) {
-    typedef __attribute__((address_space(3))) bf16x4* lds_p;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(s + rb * 2 * D + L.trlo[db]));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(s + rb * 2 * D + 16 * D + (L.trlo[db] ^ x32)));
+    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(s + rb * 2 * D + L.trlo[db]));
+    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(s + rb * 2 * D + 16 * D + (L.trlo[db] ^ x32)));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // B operand straight from global: B[k = 16*st + 8*hh + j][col = lane&31] = X[row0 + lane&31][d]
@@ -272,7 +203,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& a, int s2) {
     for (int j = 0; j < 8; ++j) p[j] = (bf16)a[8 * s2 + j];
     return p;
 }
-__device__ __forceinline__ int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // store a transposed accumulator set X^T[d][row] (d over D/32 blocks) as X[row][d] bf16, scaled
 template <int D> __device__ __forceinline__ void store_t(const f32x16 (&acc)[D / 32], bf16* dst_row, float sc, int hh) {
@@ -561,7 +491,7 @@ __global__ __launch_bounds__(512) void attn_fwd8p_kernel(const AttnParams p) {
     float mc = 0.f, l0 = 0.f, l1 = 0.f;                // reference point (scaled, log2 units) and the row sum relative to it (two chains)
     if (t_lo < t_hi) issue(t_lo, 0);
     pin_frags(qf);
-    dma_wait_all();
+    wait_vm<0>();
     __syncthreads();
     if (t_lo < t_hi) {
         // the reference: this lane's row maximum over the first half-tile (0 for a row that sees no key there)
@@ -623,7 +553,7 @@ __global__ __launch_bounds__(512) void attn_fwd8p_kernel(const AttnParams p) {
             const char* sVh = sV + half * 64 * 2 * D;
             half_tile(sKh, sVh, kv0, kv0 + 64 > kv_hi || windowed);
         }
-        dma_wait_all();                                      // the next stage has landed (issued a stage of MFMAs ago)
+        wait_vm<0>();                                      // the next stage has landed (issued a stage of MFMAs ago)
         __syncthreads();
         STAMP(5);
     }
@@ -641,7 +571,7 @@ __global__ __launch_bounds__(512) void attn_fwd8p_kernel(const AttnParams p) {
         float m = -INFINITY;
         l = 0.f;
         if (t_lo < t_hi) issue(t_lo, 0);
-        dma_wait_all();
+        wait_vm<0>();
         __syncthreads();
         for (int t = t_lo; t < t_hi; ++t) {
             const int cur = (t - t_lo) & 1;
@@ -687,7 +617,7 @@ __global__ __launch_bounds__(512) void attn_fwd8p_kernel(const AttnParams p) {
                     o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(sVh, L, 48, db), p11, o[db], 0, 0, 0);
                 }
             }
-            dma_wait_all();
+            wait_vm<0>();
             __syncthreads();
         }
         lt = l + __shfl_xor(l, 32, 64);
@@ -892,7 +822,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv8_kernel(const AttnParams p)
     };
     if (t_lo < t_hi) issue(t_lo, 0);
     pin_frags(kf);
-    dma_wait_all();
+    wait_vm<0>();
     __syncthreads();
     STAMP_DECL(8)
     for (int t = t_lo; t < t_hi; ++t) {
@@ -947,7 +877,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv8_kernel(const AttnParams p)
             }
             bf16x8 pb0 = pack8(s, 0), pb1 = pack8(s, 1), db0 = pack8(dp, 0), db1 = pack8(dp, 1);
 #ifdef SCONF_ATTN_STAMP
-            asm volatile("" : "+v"(pb0)); asm volatile("" : "+v"(pb1)); asm volatile("" : "+v"(db0)); asm volatile("" : "+v"(db1));
+            tie(pb0); tie(pb1); tie(db0); tie(db1);
 #endif
             STAMP(2);
 #pragma unroll
@@ -959,7 +889,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkdv8_kernel(const AttnParams p)
             }
             STAMP(3);
         }
-        dma_wait_all();                                // the next stage has landed (issued a stage of MFMAs ago)
+        wait_vm<0>();                                // the next stage has landed (issued a stage of MFMAs ago)
         __syncthreads();
         STAMP(4);
     }
@@ -1122,7 +1052,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq8_kernel(const AttnParams p) {
     };
     if (t_lo < t_hi) issue(t_lo, 0);
     pin_frags(qf); pin_frags(gf);
-    dma_wait_all();
+    wait_vm<0>();
     __syncthreads();
     STAMP_DECL(8)
     for (int t = t_lo; t < t_hi; ++t) {
@@ -1168,7 +1098,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq8_kernel(const AttnParams p) {
             }
             bf16x8 d0 = pack8(dp, 0), d1 = pack8(dp, 1);
 #ifdef SCONF_ATTN_STAMP
-            asm volatile("" : "+v"(d0)); asm volatile("" : "+v"(d1));
+            tie(d0); tie(d1);
 #endif
             STAMP(2);
 #pragma unroll
@@ -1178,7 +1108,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq8_kernel(const AttnParams p) {
             }
             STAMP(3);
         }
-        dma_wait_all();
+        wait_vm<0>();
         __syncthreads();
         STAMP(4);
     }

@@ -63,7 +63,7 @@ template <int D> __device__ __forceinline__ void load_frags(bf16x8 (&f)[D / 16],
         f[st] = __builtin_bit_cast(bf16x8, v);
     }
 }
-// S^T block: rows = the 32 keys of kf, columns = the 32 queries of qf.  Lane holds query (lane & 31), register r key acc_key(r, lane >> 5).
+// S^T block: rows = the 32 keys of kf, columns = the 32 queries of qf.  Lane holds query (lane & 31), register r key acc_row(r, lane >> 5).
 template <int D> __device__ __forceinline__ f32x16 st_block(const bf16x8 (&kf)[D / 16], const bf16x8 (&qf)[D / 16]) {
     f32x16 s;
 #pragma unroll
@@ -72,7 +72,6 @@ template <int D> __device__ __forceinline__ f32x16 st_block(const bf16x8 (&kf)[D
     for (int st = 0; st < D / 16; ++st) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[st], qf[st], s, 0, 0, 0);
     return s;
 }
-__device__ __forceinline__ int acc_key(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 __device__ __forceinline__ bool visible(int i, int j, int len, int wl, int wr) {
     bool ok = i < len && j >= 0 && j < len;
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(256) void attn_scores_kernel(const MapsParams p) {
             const f32x16 s = st_block<D>(kf, qf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int jl = jb + acc_key(r, hh);
+                const int jl = jb + acc_row(r, hh);
                 tile[(lane & 31) * MAPS_LD + jl] = visible(i, j0 + jl, len, p.win_left, p.win_right) ? s[r] * p.scale : -INFINITY;
             }
         }
@@ -163,7 +162,7 @@ __global__ __launch_bounds__(256) void attn_offset_partial_kernel(const MapsPara
             const f32x16 s = st_block<D>(kf[blk], qf);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int jl = jb + acc_key(r, hh);
+                const int jl = jb + acc_row(r, hh);
                 const float e = __builtin_amdgcn_exp2f(s[r] * c + nl);
                 tile[(lane & 31) * MAPS_LD + jl] = visible(i, j0 + jl, len, p.win_left, p.win_right) ? e : 0.f;
             }

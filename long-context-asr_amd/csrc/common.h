@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
+#include <initializer_list>
 #include "../../include/sconf.h"   // the public C ABI: every SCONF_API definition is compiled against its declaration
 
 typedef __bf16 bf16;
@@ -14,6 +16,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define SCONF_API extern "C" __attribute__((visibility("default")))
+#include "gfx950.h"                // inline-asm, LDS-DMA, wait, tie and stamp primitives (needs the vector types above)
 
 // ---- error reporting (C ABI: non-zero return + sconf_last_error()) ---------------------------
 int sconf_set_error(const char* fmt, ...);
@@ -81,6 +84,9 @@ __device__ __forceinline__ void store4(bf16* p, const float (&v)[4]) {
 __device__ __forceinline__ void store4(float* p, const float (&v)[4]) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
 }
+// the same by a compile-time width W (4 or 8)
+template <int W, typename T> __device__ __forceinline__ void loadv(const T* p, float (&v)[W]) { if constexpr (W == 8) load8(p, v); else load4(p, v); }
+template <int W, typename T> __device__ __forceinline__ void storev(T* p, const float (&v)[W]) { if constexpr (W == 8) store8(p, v); else store4(p, v); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -147,6 +153,21 @@ __device__ __forceinline__ float dgeluf_(float x) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline int conv_out(long n) { return (int)((n - 1) / 2 + 1); }          // output length of a 3-tap, stride-2, pad-1 convolution
+// CUs of the current device, asked for once; 256 (an MI355X) if the runtime does not say
+static inline int num_cus() {
+    static int cus = 0;
+    if (!cus) { const int n = sconf_num_cus(); cus = n > 0 ? n : 256; }
+    return cus;
+}
+// raises the kernels' dynamic-LDS limit the first time it is reached; `done` is a function-local static of the call site
+static inline void lds_limit_once(bool& done, std::initializer_list<const void*> kernels, size_t bytes) {
+    if (!done) for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    done = true;
+}
+// read on EVERY call (tests flip them inside one process): an integer override, and SCONF_SUB_MFMA=0 (subsampler on its VALU kernels)
+static inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+static inline bool sub_mfma_off() { const char* e = getenv("SCONF_SUB_MFMA"); return e && e[0] == '0'; }
 
 // ---- fixed-order accumulation ----------------------------------------------------------------
 // Float atomics from many workgroups onto one address add up in arrival order, which changes from run to run, and so would

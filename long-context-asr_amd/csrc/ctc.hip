@@ -23,22 +23,19 @@
 //                  10230 states do not fit the LDS in f64 and run the same code with f32 state.)
 //   3. grad     one workgroup per (b,t) row: occupancy scattered into an LDS histogram over classes, then
 //               grad = g * (exp(lp) - occupancy)   [ATen convention; zero for t >= input_length].
+#ifdef CTC_STAMP
+#define SCONF_STAMPS                 // gfx950.h: STAMP_DECL / STAMP are live in this file
+#endif
 #include "common.h"
-#include <stdlib.h>
 #include <algorithm>
 
 namespace {
 
 #ifdef CTC_STAMP
 __device__ unsigned long long g_ctc_stamps[16 * 8];
-#define CSTAMP_DECL unsigned long long st_acc_[8] = {}, st_last_ = 0; { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_last_ = t_; }
-#define CSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                      __builtin_amdgcn_sched_barrier(0); st_acc_[i] += t_ - st_last_; st_last_ = t_; } while (0)
-#define CSTAMP_OUT do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) g_ctc_stamps[(threadIdx.x >> 6) * 8 + i_] = st_acc_[i_]; } while (0)
+#define STAMP_OUT do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) g_ctc_stamps[(threadIdx.x >> 6) * 8 + i_] = st_acc_[i_]; } while (0)
 #else
-#define CSTAMP_DECL
-#define CSTAMP(i)
-#define CSTAMP_OUT
+#define STAMP_OUT
 #endif
 
 // log(e^a + e^b + e^c): the largest term contributes exactly 1, so only the median and the minimum need an exponential
@@ -132,21 +129,6 @@ __global__ __launch_bounds__(256) void ctc_gather_kernel(const float* __restrict
     }
 }
 
-// LDS-DMA of 4 bytes per lane through a buffer descriptor, as inline asm: the builtin makes hipcc wait for EVERY pending DMA
-// (vmcnt(0)) in front of the next LDS read of any kind (attention.hip has the long story).  lds_base (uniform) + 4 * lane <- srd[voff].
-typedef __amdgpu_buffer_rsrc_t ctc_srd_t;
-__device__ __forceinline__ ctc_srd_t ctc_make_srd(const void* base, long nbytes) {
-    const unsigned long a = (unsigned long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const unsigned nb = __builtin_amdgcn_readfirstlane((unsigned)(nbytes > 0xffffffffL ? 0xffffffffL : nbytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long)hi << 32) | lo), 0, nb, 0x00020000);
-}
-__device__ __forceinline__ void ctc_dma_dword(ctc_srd_t srd, unsigned voff, unsigned soff, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %3, %4, %1 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep), "+s"(soff), "+s"(lds_base) : "v"(voff), "s"(srd) : "memory");
-}
-
 // One workgroup per (sample, direction).  MAXS = max lattice states per thread; LT = type of the recursion's state (double; float
 // only for lattices that do not fit the LDS in f64).  The recursion runs in log2 units relative to nothing (absolute, in LT); what
 // is STORED for the gradient pass is natural-log, f32, relative to the frame's offset A_t (f64, written to offs), which follows the
@@ -234,12 +216,13 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
         }
     };
     // Long lattices (LONG): the emissions arrive by LDS-DMA, one frame ahead, instead of as MAXS strided dword loads per thread and
-    // frame (which, with the row stores, filled the memory pipeline: 3.4 k of 12 k cycles per frame went into ISSUING them).  Every
+    // frame (which, with the row stores, filled the memory pipeline: 3.4 k of 12 k cycles per frame went into ISSUING them).  The DMA
+    // is dma_dword, inline asm: gfx950.h has the long story of what the builtin would make hipcc wait for.  Every
     // blank state has the same emission, so what a wave needs is [blank, the labels of its own state range]: each wave stages exactly
     // that into a segment of its own - its vmcnt(0) covers everything it reads, and no barrier orders the DMA against the reads.
     constexpr int SEGN = 64 * (MAXS / 2 + 1);            // floats per wave segment: 1 + 32 MAXS (+ 1) entries, whole pieces of 64
     float* stage = reinterpret_cast<float*>(reinterpret_cast<char*>(wm) + 64) + wave * SEGN;
-    const unsigned stage_lds = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)stage;
+    const unsigned stage_lds = lds_addr(stage);
     // the wave's states in natural coordinates, and its first label
     const int wsp0 = wave * 64 * MAXS, wsp1 = min(wsp0 + 64 * MAXS - 1, L - 1);
     const int s_lo = is_beta ? L - 1 - wsp1 : wsp0, jl0 = max(s_lo, 0) >> 1;
@@ -247,12 +230,12 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
         if (wsp0 >= L) return;
         const int Tu = __builtin_amdgcn_readfirstlane(T), iu = __builtin_amdgcn_readfirstlane(i);
         const int t = is_beta ? Tu - 1 - min(iu, Tu - 1) : min(iu, Tu - 1);
-        const ctc_srd_t esrd = ctc_make_srd(lg, (long)N * Lmax * 4);
+        const srd_t esrd = make_srd(lg, (long)N * Lmax * 4);
 #pragma unroll
         for (int pc = 0; pc < MAXS / 2 + 1; ++pc) {
             const int e = pc * 64 + (tid & 63);            // entry 0: the blank; entry e: label jl0 + e - 1
             const int src = e == 0 ? 0 : 2 * min(jl0 + e - 1, max(S - 1, 0)) + 1;
-            ctc_dma_dword(esrd, (unsigned)(((long)t * Lmax + min(src, Lmax - 1)) * 4), 0u,        // (row offset in the per-lane part: < 4 GB per sample)
+            dma_dword(esrd, (unsigned)(((long)t * Lmax + min(src, Lmax - 1)) * 4), 0u,        // (row offset in the per-lane part: < 4 GB per sample)
                           (unsigned)__builtin_amdgcn_readfirstlane((int)(stage_lds + (unsigned)(pc * 256))));
         }
     };
@@ -265,9 +248,9 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
     };
     if constexpr (LONG) {
         dma_frame(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         read_stage(pf[0]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         dma_frame(1);
     } else {
         load_group(pf, 0);
@@ -277,11 +260,11 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
             for (int k = 0; k < MAXS; ++k) pf[j][k] = fmaxf(pf[j][k], -1e30f);
     }
     double A = 0.0;                                      // offset of the stored rows, log2 units
-    CSTAMP_DECL
+    STAMP_DECL(8)
     const int w0 = wave * 64 * MAXS, w1 = w0 + 64 * MAXS - 1;   // the wave's range of states
     for (int i0 = 0; i0 < T; i0 += G) {
         if constexpr (!LONG) load_group(nx, i0 + G);     // prefetch the next G time steps
-        CSTAMP(4);
+        STAMP(4);
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             const int i = i0 + j;
@@ -309,7 +292,7 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
                             LT pv[CH + 2];
 #pragma unroll
                             for (int q = 0; q < CH + 2; ++q) pv[q] = prev[sp0 + k0 - 2 + q];
-                            if (k0 == 0) CSTAMP(0);
+                            if (k0 == 0) STAMP(0);
                             LT c[CH], m[CH], base[CH];
                             float e0[CH], e1[CH], e2[CH];
 #pragma unroll
@@ -341,7 +324,7 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
                                 }
                             }
                         }
-                        CSTAMP(1);
+                        STAMP(1);
                     }
                 } else {
 #pragma unroll
@@ -352,15 +335,15 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
                     mine = wave_max_dpp(mine);
                     if ((tid & 63) == 0) wm[wave] = mine;
                 }
-                CSTAMP(2);
+                STAMP(2);
                 if constexpr (LONG) {                      // next frame's emissions (DMA issued a frame ago by this wave), then the frame after
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    wait_vm<0>();
                     read_stage(nx[0]);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the segment has been read: it may be overwritten
+                    wait_lgkm0();      // the segment has been read: it may be overwritten
                     dma_frame(i + 2);
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                CSTAMP(3);
+                wait_lgkm0_barrier();
+                STAMP(3);
                 // Long lattices (COOP): the row leaves for the gradient pass from its LDS copy, lanes on consecutive states (a thread's own MAXS states sit
                 // 4 MAXS bytes apart from its neighbour's: ten strided dword stores per thread and frame filled the memory pipeline of the
                 // 8 k-state lattices).  Row i & 1 is not written again before the barrier of frame i + 1.
@@ -380,10 +363,10 @@ __global__ __launch_bounds__(1024) void ctc_alphabeta_kernel(const float* __rest
         for (int j = 0; j < G; ++j)
 #pragma unroll
             for (int k = 0; k < MAXS; ++k) pf[j][k] = fmaxf(nx[j][k], -1e30f);            // an emission of -inf must stay finite in the recursion (LONG: clamped already)
-        CSTAMP(5);
+        STAMP(5);
     }
-    CSTAMP_OUT;
-    if constexpr (LONG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no staging DMA in flight when the waves end
+    STAMP_OUT;
+    if constexpr (LONG) wait_vm<0>();      // no staging DMA in flight when the waves end
     if (!is_beta && tid == 0) {
         const LT* last = lat + ((T - 1) & 1) * W + 2;
         const double v = -(double)lse3_log2(last[L - 1], L > 1 ? last[L - 2] : NEG, NEG) * LN2_D;
@@ -623,7 +606,7 @@ SCONF_API int sconf_ctc_fwd_logits(const float* logits, const int32_t* targets, 
 
 static int ctc_bwd_slabs() {                            // workgroups of the fused gradient kernel (each keeps a slab of column sums)
     static int v = 0;
-    if (!v) { const char* e = getenv("SCONF_CTC_BWD_SLABS"); v = e ? atoi(e) : 0; if (v < 64 || v > 65536) { const int n = sconf_num_cus(); v = 12 * (n > 0 ? n : 256); } }   // 6 resident per CU: whole rounds (2048: 2.78 ms, 3072: 2.63 at B = 128)
+    if (!v) { const char* e = getenv("SCONF_CTC_BWD_SLABS"); v = e ? atoi(e) : 0; if (v < 64 || v > 65536) v = 12 * num_cus(); }   // 6 resident per CU: whole rounds (2048: 2.78 ms, 3072: 2.63 at B = 128)
     return v;
 }
 #define CTC_BWD_SLABS ctc_bwd_slabs()

@@ -18,7 +18,6 @@
 // owns 4 *consecutive output columns* of one row: bias/residual/aux traffic and the C store are
 // 8-16 B per lane.  Block ids are remapped so that consecutive tiles stay on one XCD (shared L2).
 #include "gemm_tile.h"
-#include <stdlib.h>
 #include <algorithm>
 
 namespace {
@@ -65,7 +64,7 @@ __device__ __forceinline__ void tile_lstore(const uint4 (&r)[4], char* s, int ti
     }
 }
 
-// ---- global -> LDS directly (LDS-DMA, global_load_lds_dwordx4): no staging VGPRs, no ds_write ----------------
+// ---- global -> LDS directly (LDS-DMA, 16 bytes per lane): no staging VGPRs, no ds_write ----------------
 // The LDS destination of one wave-instruction is wave-uniform base + lane*16 (linear), so the swizzle is applied to
 // the per-lane SOURCE address and undone by the same involution on the fragment read (rule "both sides or neither").
 // Rows beyond the matrix are clamped to a valid row (their products are never stored); the K range must be whole
@@ -91,8 +90,6 @@ template <bool KS, bool BIMG> struct GldsOffs {
 };
 template <bool KS, bool BIMG>
 __device__ __forceinline__ void tile_glds(const bf16* __restrict__ P, long ld, int k0, const GldsOffs<KS, BIMG>& o, char* s, int tid) {
-    typedef const __attribute__((address_space(1))) void* gptr;
-    typedef __attribute__((address_space(3))) void* lptr;
     const char* base = reinterpret_cast<const char*>(P) + (KS ? (long)k0 * ld * 2 : (long)k0 * 2);   // wave-uniform
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -119,9 +116,8 @@ __device__ __forceinline__ bf16x8 frag_read(const char* s, int rbase, int j, int
         const int col = rbase + 16 * j + 4 * p;               // strided operands keep the natural column order (see epilogue)
         const int chunk = col >> 3, sub = (col & 4) * 2;
         const int k0 = kk * 32 + 8 * g + q, k1 = k0 + 4;
-        typedef __attribute__((address_space(3))) bf16x4* lds_p;
-        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(s + k0 * 256 + ((chunk ^ swz_strided(k0)) << 4) + sub));
-        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(s + k1 * 256 + ((chunk ^ swz_strided(k1)) << 4) + sub));
+        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(s + k0 * 256 + ((chunk ^ swz_strided(k0)) << 4) + sub));
+        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(s + k1 * 256 + ((chunk ^ swz_strided(k1)) << 4) + sub));
         return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     }
 }
@@ -338,20 +334,16 @@ int gemm_launch(const GemmParams& p, int layout, hipStream_t stream) {
     dim3 grid(ntiles * p.splits), block(256);
     const size_t shmem = 4 * TILE_BYTES;
     static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[6] = {(const void*)gemm_kernel<false, false, false>, (const void*)gemm_kernel<false, true, false>,
+    lds_limit_once(attr_set, {(const void*)gemm_kernel<false, false, false>, (const void*)gemm_kernel<false, true, false>,
                               (const void*)gemm_kernel<true, true, false>, (const void*)gemm_kernel<false, false, true>,
-                              (const void*)gemm_kernel<false, true, true>, (const void*)gemm_kernel<true, true, true>};
-        for (int i = 0; i < 6; ++i) (void)hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        attr_set = true;
-    }
+                              (const void*)gemm_kernel<false, true, true>, (const void*)gemm_kernel<true, true, true>}, shmem);
     // LDS-DMA staging needs whole 64-deep K tiles (no zero fill), at least one full 8-row chunk to clamp to, and
     // operands addressable with 32-bit byte offsets from a uniform base; register staging takes every other shape.
     const bool glds = p.K % BK == 0 && p.M >= 8 && p.N >= 8 &&
                       (long)(aks ? p.K : p.M) * p.lda * 2 < (1L << 32) && (long)(bks ? p.K : p.N) * p.ldb * 2 < (1L << 32);
     if (glds) {
         static int slots = 0;
-        if (!slots) { int n = sconf_num_cus(); slots = 2 * (n > 0 ? n : 256); }
+        if (!slots) slots = 2 * num_cus();
         grid.x = std::min(ntiles * p.splits, slots);              // persistent: <= 2 resident workgroups per CU
         if (layout == 0)      hipLaunchKernelGGL((gemm_kernel<false, false, true>), grid, block, shmem, stream, p);
         else if (layout == 1) hipLaunchKernelGGL((gemm_kernel<false, true, true>), grid, block, shmem, stream, p);

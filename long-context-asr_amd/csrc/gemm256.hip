@@ -25,9 +25,11 @@
 //        row included) makes that true for all waves before any L_(P+1) read.  Issue phases: A0, B0 of K-tile s+2 in
 //        (s, q2), (s, q3); B1, A1 of K-tile s+1 in (s, q0), (s, q1); read phases: A0/B0 q0, B1 q1, A1 q2 - always >= 5
 //        phases after the issue.
+#ifdef SCONF_GEMM_STAMP
+#define SCONF_STAMPS                 // gfx950.h: STAMP_DECL / STAMP are live in this file
+#endif
 #include "gemm_tile.h"
 #include <algorithm>
-#include <stdlib.h>
 #include <stdio.h>
 
 namespace {
@@ -40,10 +42,6 @@ constexpr int HT = 128 * 64 * 2;                   // one half-tile image, 16 Ki
 constexpr int BUF = 4 * HT;                        // A0 | A1 | B0 | B1
 constexpr int GM2 = 4;                             // row panels per L2 patch (4 x 8 tiles = the 32 workgroups of one XCD);
                                                    // 8 x 4 when the output is >= 8 tiles wide (measured +2-4 % at N >= 2304)
-
-typedef const __attribute__((address_space(1))) void* gptr;
-typedef __attribute__((address_space(3))) void* lptr;
-typedef __attribute__((address_space(3))) bf16x4* lds_p4;
 
 // K-contiguous images are [rows][64 k] with a 16-B-chunk XOR swizzle per row.
 // A image: the half's 128 rows in natural order, read 16 consecutive rows at a time.
@@ -93,10 +91,10 @@ __device__ __forceinline__ void dma_half(const char* base, const unsigned (&off)
 // Transposed LDS read as inline asm.  Through the builtin, hipcc puts an unconditional `s_waitcnt vmcnt(0)` in front of the
 // reads (it cannot tell them from the in-flight LDS-DMA destinations), which drains the whole prefetch pipeline twice per
 // K-tile - the reason the K-strided (weight-gradient) kernel sat parked 57 % of its wave-cycles.  The asm form is invisible to
-// that logic AND to the compiler's lgkmcnt tracking: the consumer must run LGKM_FENCE (wait + register tie) before using it.
+// that logic AND to the compiler's lgkmcnt tracking: the consumer must run wait_lgkm0() and tie() the result before using it.
 __device__ __forceinline__ bf16x4 lds_read_tr(const char* p) {
     bf16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"((unsigned)(unsigned long)(lptr)p));
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr(p)));
     return v;
 }
 template <int OFF> __device__ __forceinline__ bf16x4 lds_read_tr_off(unsigned a) {
@@ -110,14 +108,12 @@ template <int OFF> __device__ __forceinline__ bf16x4 lds_read_tr_off(unsigned a)
 __device__ __forceinline__ void frag_pair_ks(const char* s, int col, int lane, bf16x8& f0, bf16x8& f1) {
     const int a = lane & 15, q = a >> 2, g = lane >> 4;
     const int chunk = col >> 3, sub = (col & 4) * 2, k0 = 8 * g + q;
-    const unsigned base = (unsigned)(unsigned long)(lptr)(s + k0 * 256 + ((chunk ^ swz_strided(k0)) << 4) + sub);
+    const unsigned base = lds_addr(s + k0 * 256 + ((chunk ^ swz_strided(k0)) << 4) + sub);
     const bf16x4 l0 = lds_read_tr_off<0>(base), h0 = lds_read_tr_off<1024>(base);
     const bf16x4 l1 = lds_read_tr_off<8192>(base), h1 = lds_read_tr_off<9216>(base);
     f0 = __builtin_shufflevector(l0, h0, 0, 1, 2, 3, 4, 5, 6, 7);
     f1 = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-#define LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define TIE(x) asm volatile("" : "+v"(x))
 // 16 x 32 MFMA fragments.  K-contiguous: one ds_read_b128; K-strided ([64 k][128 cols] image): two transposed reads.
 template <bool KS> __device__ __forceinline__ bf16x8 frag_a(const char* s, int wr, int i, int kk, int lane) {
     if (!KS) {
@@ -441,26 +437,20 @@ __host__ __device__ __forceinline__ int epilogue_kind(const GemmParams& p) {
         else epilogue256<SCONF_ACT_SMAXBWD, false, false, JH_, 4, false, DEEPV>(p, acc, cit, wr, wc, lane);                         \
     } while (0)
 
-#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-// In-kernel time stamps (cdna_hip_programming.md section 7), DIAGNOSTIC build only (make EXTRA=-DSCONF_GEMM_STAMP; tools/gemm_stamp.py):
+// In-kernel time stamps (gfx950.h), DIAGNOSTIC build only (make EXTRA=-DSCONF_GEMM_STAMP; tools/gemm_stamp.py):
 // per wave, cycle sums of the fragment reads, the LDS-DMA issue, the counted wait, the waits at the two barriers of a phase, the
 // MFMA clusters and the epilogue.  Nothing of it exists in the product build.
 #ifdef SCONF_GEMM_STAMP
 __device__ unsigned long long g_gemm_stamps[256 * 8 * 8];
-#define GSTAMP_DECL unsigned long long st_acc_[8] = {}, st_last_ = 0; { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_last_ = t_; }
-#define GSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                       __builtin_amdgcn_sched_barrier(0); st_acc_[i] += t_ - st_last_; st_last_ = t_; } while (0)
-#define GSTAMP_OUT do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) for (int i_ = 0; i_ < 8; ++i_) g_gemm_stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + i_] = st_acc_[i_]; } while (0)
+#define STAMP_OUT do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 256) for (int i_ = 0; i_ < 8; ++i_) g_gemm_stamps[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + i_] = st_acc_[i_]; } while (0)
 #else
-#define GSTAMP_DECL
-#define GSTAMP(i)
-#define GSTAMP_OUT
+#define STAMP_OUT
 #endif
 // leave the 4 youngest half-tiles in flight: 2 + 2 + 2 + JH DMA instructions per wave
 template <int JH> __device__ __forceinline__ void wait_window(bool streaming) {
-    if (!streaming) VMCNT(0);
-    else if (JH == 2) VMCNT(8);
-    else VMCNT(7);
+    if (!streaming) wait_vm<0>();
+    else if (JH == 2) wait_vm<8>();
+    else wait_vm<7>();
 }
 
 template <bool KS, int EK = -1>
@@ -507,12 +497,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     pc.advance(p, sc);
     issue_a(pc, 0); issue_b(pc, 0);
     if (pc.valid) wait_window<JH>(true);             // A0, B0 of K-tile 0 have landed
-    else VMCNT(4);
+    else wait_vm<4>();
     __builtin_amdgcn_s_barrier();
 
     int cur = 0;
     bf16x8 fa[4][2], blo[2][2], bhi[JH][2];
-    GSTAMP_DECL
+    STAMP_DECL(8)
     while (true) {
         if (wr) __builtin_amdgcn_s_barrier();         // stagger the second wave row by one barrier
         for (int kt = 0; kt < cit.nkt; ++kt) {
@@ -535,21 +525,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int kk = 0; kk < 2; ++kk) fa[i][kk] = frag_a<KS>(buf, wr, i, kk, lane);
                 }
             }
-            GSTAMP(6);
+            STAMP(6);
             issue_b(pc, 1);
-            GSTAMP(7);
+            STAMP(7);
             wait_window<JH>(pc.valid);
-            GSTAMP(0);
+            STAMP(0);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(1);
+            STAMP(1);
             if constexpr (KS) {
-                LGKM0();
+                wait_lgkm0();
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) TIE(blo[j][kk]);
+                    for (int j = 0; j < 2; ++j) tie(blo[j][kk]);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) TIE(fa[i][kk]);
+                    for (int i = 0; i < 4; ++i) tie(fa[i][kk]);
                 }
             }
             __builtin_amdgcn_s_setprio(1);
@@ -561,9 +551,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int j = 0; j < 2; ++j)
                         acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(blo[j][kk], fa[i][kk], acc[0][i][j], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
-            GSTAMP(2);
+            STAMP(2);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(3);
+            STAMP(3);
             // ---- q1: B-hi -> acc[0][.][2..3] ---------------------------------------------------------------------
 #pragma unroll
             for (int j = 0; j < JH; ++j) {
@@ -573,19 +563,19 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int kk = 0; kk < 2; ++kk) bhi[j][kk] = frag_b<KS, false>(buf + 3 * HT, wc, j, kk, lane);
                 }
             }
-            GSTAMP(6);
+            STAMP(6);
             issue_a(pc, 1);
-            GSTAMP(7);
+            STAMP(7);
             wait_window<JH>(pc.valid);
-            GSTAMP(0);
+            STAMP(0);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(1);
+            STAMP(1);
             if constexpr (KS) {
-                LGKM0();
+                wait_lgkm0();
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                    for (int j = 0; j < JH; ++j) TIE(bhi[j][kk]);
+                    for (int j = 0; j < JH; ++j) tie(bhi[j][kk]);
             }
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -596,9 +586,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int j = 0; j < JH; ++j)
                         acc[0][i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bhi[j][kk], fa[i][kk], acc[0][i][2 + j], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
-            GSTAMP(2);
+            STAMP(2);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(3);
+            STAMP(3);
             // ---- q2: A-hi -> acc[1][.][2..3] ---------------------------------------------------------------------
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -609,19 +599,19 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                 }
             }
             pc.advance(p, sc);
-            GSTAMP(6);
+            STAMP(6);
             issue_a(pc, 0);
-            GSTAMP(7);
+            STAMP(7);
             wait_window<JH>(pc.valid);
-            GSTAMP(0);
+            STAMP(0);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(1);
+            STAMP(1);
             if constexpr (KS) {
-                LGKM0();
+                wait_lgkm0();
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) TIE(fa[i][kk]);
+                    for (int i = 0; i < 4; ++i) tie(fa[i][kk]);
             }
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -632,17 +622,17 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int j = 0; j < JH; ++j)
                         acc[1][i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bhi[j][kk], fa[i][kk], acc[1][i][2 + j], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
-            GSTAMP(2);
+            STAMP(2);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(3);
+            STAMP(3);
             // ---- q3: (B-lo still in registers) -> acc[1][.][0..1] ------------------------------------------------
-            GSTAMP(6);
+            STAMP(6);
             issue_b(pc, 0);
-            GSTAMP(7);
+            STAMP(7);
             wait_window<JH>(pc.valid);
-            GSTAMP(0);
+            STAMP(0);
             __builtin_amdgcn_s_barrier();
-            GSTAMP(1);
+            STAMP(1);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
@@ -652,9 +642,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int j = 0; j < 2; ++j)
                         acc[1][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(blo[j][kk], fa[i][kk], acc[1][i][j], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
-            GSTAMP(2);
+            STAMP(2);
             if (!(wr && last)) __builtin_amdgcn_s_barrier();   // the lagging row goes straight into its epilogue
-            GSTAMP(3);
+            STAMP(3);
             cur ^= 1;
         }
         // ---- epilogue: both wave rows concurrently; one specialised, contiguous code path per (activation, residual) ------
@@ -667,15 +657,15 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 2 + JH; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        GSTAMP(4);                                    // epilogue (+ accumulator clears)
+        STAMP(4);                                    // epilogue (+ accumulator clears)
         __builtin_amdgcn_s_barrier();                 // re-align the two wave rows
-        GSTAMP(5);
+        STAMP(5);
         cv += gridDim.x;
         if (cv >= sc.total) break;
         cit = item_coords(p, sc, cv);
     }
-    VMCNT(0);
-    GSTAMP_OUT;
+    wait_vm<0>();
+    STAMP_OUT;
 }
 
 // ---- 256x192 tile, NT, THREE phases per K-tile -------------------------------------------------------------------------
@@ -731,7 +721,7 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
     issue_a(pc, 0); issue_b(pc, 0); issue_a(pc, 1); issue_b(pc, 1);
     pc.advance(p, sc);
     issue_a(pc, 0); issue_b(pc, 0);
-    if (pc.valid) VMCNT(7); else VMCNT(3);           // A0, B0 of K-tile 0 have landed
+    if (pc.valid) wait_vm<7>(); else wait_vm<3>();           // A0, B0 of K-tile 0 have landed
     __builtin_amdgcn_s_barrier();
 
     int cur = 0;
@@ -811,7 +801,7 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
         if (cv >= sc.total) break;
         cit = item_coords(p, sc, cv);
     }
-    VMCNT(0);
+    wait_vm<0>();
 }
 
 }  // namespace
@@ -829,11 +819,6 @@ static int pick_width(const GemmParams& p, int layout, int cus) {
     }
     return bw;
 }
-static int num_cus_cached() {
-    static int cus = 0;
-    if (!cus) { const int n = sconf_num_cus(); cus = n > 0 ? n : 256; }
-    return cus;
-}
 
 bool sconf_gemm256_eligible(const GemmParams& p, int layout) {
     if (layout != 0 && layout != 2) return false;
@@ -844,31 +829,27 @@ bool sconf_gemm256_eligible(const GemmParams& p, int layout) {
                (p.act == SCONF_ACT_SMAXBWD && !p.resid && !p.bias && !p.out_f32 && !p.pre && p.splits == 1))) return false;
     // 32-bit per-lane source offsets relative to a half-tile base
     if ((ks ? 64 : 256) * p.lda * 2 >= (1L << 32) || (ks ? 64 : 256) * p.ldb * 2 >= (1L << 32)) return false;
-    const int cus = num_cus_cached();
+    const int cus = num_cus();
     const int w = pick_width(p, layout, cus);
     if (!w || (p.act == SCONF_ACT_SMAXBWD && w != 256)) return false;
     // one workgroup per CU: below ~3/4 of a round the 128x128 kernel (2 per CU, 4x the tiles) fills the chip better
     return (long)(p.M / TM) * (p.N / w) * p.splits * 4 >= 3L * cus;
 }
 
-int sconf_gemm256_width(const GemmParams& p, int layout) { return pick_width(p, layout, num_cus_cached()); }
+int sconf_gemm256_width(const GemmParams& p, int layout) { return pick_width(p, layout, num_cus()); }
 
 int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
     static bool attr_set = false;
     const size_t shmem = 2 * BUF;
-    if (!attr_set) {
-        const void* fns[] = {(const void*)gemm256_kernel<false>, (const void*)gemm256_kernel<true>,
+    lds_limit_once(attr_set, {(const void*)gemm256_kernel<false>, (const void*)gemm256_kernel<true>,
                              (const void*)gemm256_kernel<false, 0>, (const void*)gemm256_kernel<false, 1>, (const void*)gemm256_kernel<false, 2>,
                              (const void*)gemm256_kernel<false, 3>, (const void*)gemm256_kernel<false, 4>, (const void*)gemm256_kernel<false, 5>,
                              (const void*)gemm256_kernel<false, 7>, (const void*)gemm256_kernel<false, 8>, (const void*)gemm256_kernel<false, 9>,
                              (const void*)gemm256_kernel<false, 10>, (const void*)gemm256_kernel<false, 11>, (const void*)gemm256_kernel<false, 12>,
                              (const void*)gemm192_kernel<11>, (const void*)gemm192_kernel<12>, (const void*)gemm192_kernel<-1>, (const void*)gemm192_kernel<0>,
                              (const void*)gemm192_kernel<1>, (const void*)gemm192_kernel<2>, (const void*)gemm192_kernel<3>, (const void*)gemm192_kernel<4>,
-                             (const void*)gemm192_kernel<5>, (const void*)gemm192_kernel<9>};
-        for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        attr_set = true;
-    }
-    const int cus = num_cus_cached();
+                             (const void*)gemm192_kernel<5>, (const void*)gemm192_kernel<9>}, shmem);
+    const int cus = num_cus();
     const int w = pick_width(p, layout, cus);
     const int total = (p.M / TM) * (p.N / w) * p.splits;
     dim3 grid(std::min(total, cus)), block(512);

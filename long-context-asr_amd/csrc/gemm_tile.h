@@ -38,11 +38,6 @@ template <bool BIMG> __device__ __forceinline__ int swz_kc(int row) {
 // ---- fused epilogue, per run of W (4 or 8) consecutive output columns of one row ---------------------------------------------
 //   out = resid + alpha * act(acc + bias)        (act may also save gelu' / the pre-activation, or multiply by aux)
 // Split in two steps so that a caller can issue the aux / residual loads of all its runs before any math or store.
-template <int W> __device__ __forceinline__ void loadv(const bf16* p, float (&v)[W]) { if constexpr (W == 8) load8(p, v); else load4(p, v); }
-template <int W> __device__ __forceinline__ void loadv(const float* p, float (&v)[W]) { if constexpr (W == 8) load8(p, v); else load4(p, v); }
-template <int W> __device__ __forceinline__ void storev(bf16* p, const float (&v)[W]) { if constexpr (W == 8) store8(p, v); else store4(p, v); }
-template <int W> __device__ __forceinline__ void storev(float* p, const float (&v)[W]) { if constexpr (W == 8) store8(p, v); else store4(p, v); }
-
 template <int W> struct EpiIn { float ax[W], rs[W]; };
 __device__ __forceinline__ bool epi_uses_aux(const GemmParams& p) {
     return p.act == SCONF_ACT_DGELU || p.act == SCONF_ACT_DSILU || p.act == SCONF_ACT_MULAUX || p.act == SCONF_ACT_SMAXBWD;

@@ -10,7 +10,6 @@
 // grid-stride loop of rows, reduced across the workgroup's waves in LDS and flushed with one f32 atomic per
 // column per workgroup.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -270,10 +269,8 @@ __global__ __launch_bounds__(1024) void norm_bwd_reduce_kernel(const float* __re
 // (x 4 instantiations of every (mode, width, dtype) combination: a 10 MB object for a LayerNorm); the measured-best pair is now fixed.
 constexpr int NBW = 8;
 static int bwd_maxgrid() {
-    static int cus = 0;
-    if (!cus) { const int n = sconf_num_cus(); cus = n > 0 ? n : 256; }
     if (const char* e = getenv("SCONF_NORM_BWD_GRID")) { const int v = atoi(e); if (v > 0) return v; }      // benchmarking
-    return cus;
+    return num_cus();
 }
 
 template <int MODE, int NIT>

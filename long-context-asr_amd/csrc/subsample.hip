@@ -9,7 +9,6 @@
 // backward), which halves the HBM traffic of the largest activations of the model.  H axis = time,
 // W axis = frequency, exactly as the reference's Conv2d on (B,1,T,F).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -18,8 +17,6 @@ constexpr int CG8 = 8;                               // channels per thread (16-
 // Thread geometry shared by the conv kernels: a thread OWNS one group of 8 channels for its whole life (its 72 filter
 // taps + bias sit in registers) and walks output positions; a workgroup = cgs channel groups x PL position lanes, so
 // each iteration touches PL x (C*2) contiguous bytes.  blockIdx.y = batch item; all index math is 32-bit.
-template <int W> __device__ __forceinline__ void gemm_free_loadv(const bf16* p, float (&v)[W]) { if constexpr (W == 8) load8(p, v); else load4(p, v); }
-template <int W> __device__ __forceinline__ void gemm_free_storev(bf16* p, const float (&v)[W]) { if constexpr (W == 8) store8(p, v); else store4(p, v); }
 
 struct Geo {
     int cg, plane, c0;
@@ -158,9 +155,9 @@ __global__ __launch_bounds__(512) void dwconv2d_bwd_kernel(const bf16* __restric
 #pragma unroll
                 for (int bb = 0; bb < 2; ++bb) {
                     const int to = min(max(to0 - a, 0), To - 1), fo = min(max(fo0 - bb, 0), Fo - 1);
-                    gemm_free_loadv<CW>(gb + ((long)to * Fo + fo) * C, gq[a][bb]);
+                    loadv<CW>(gb + ((long)to * Fo + fo) * C, gq[a][bb]);
                 }
-            float pv[CW], sg[CW], sv[CW]; gemm_free_loadv<CW>(pb + (long)p * C, pv);
+            float pv[CW], sg[CW], sv[CW]; loadv<CW>(pb + (long)p * C, pv);
 #pragma unroll
             for (int e = 0; e < CW; ++e) { sg[e] = sigmoidf_(pv[e]); sv[e] = pv[e] * sg[e]; }
             float acc[CW];
@@ -189,7 +186,7 @@ __global__ __launch_bounds__(512) void dwconv2d_bwd_kernel(const bf16* __restric
             }
 #pragma unroll
             for (int e = 0; e < CW; ++e) { acc[e] *= sg[e] * (1.f + pv[e] * (1.f - sg[e])); gcs[e] += (float)(bf16)acc[e]; }   // sums of what is stored
-            gemm_free_storev<CW>(ob + (long)p * C, acc);
+            storev<CW>(ob + (long)p * C, acc);
         }
     }
 #pragma unroll
@@ -563,7 +560,7 @@ inline LaunchGeo geo_for(int64_t C, int64_t B, long npos, long target_blocks) {
 SCONF_API int sconf_sub_conv0_fwd(const void* x, int x_dtype, const float* w, const float* bias, void* y,
                                   int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     SUB_REQ("sconf_sub_conv0_fwd");
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1);
+    const int T2 = conv_out(T), F2 = conv_out(F);
     if (B * T2 * F2 == 0) return 0;
     const LaunchGeo g = geo_for(C, B, (long)T2 * F2, 16384);
     if (x_dtype == SCONF_F32) hipLaunchKernelGGL((conv0_fwd_kernel<float>), g.grid, dim3(g.threads), 0, stream, (const float*)x, w, bias, (bf16*)y, (int)F, (int)T, (int)C, T2, F2, g.PL, g.iters);
@@ -577,7 +574,7 @@ SCONF_API int sconf_sub_conv0_fwd(const void* x, int x_dtype, const float* w, co
 SCONF_API int sconf_sub_dwconv_fwd(const void* x, const float* w, const float* bias, void* y,
                                    int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream) {
     SUB_REQ("sconf_sub_dwconv_fwd");
-    const int To = (int)((Ti - 1) / 2 + 1), Fo = (int)((Fi - 1) / 2 + 1);
+    const int To = conv_out(Ti), Fo = conv_out(Fi);
     if (B * To * Fo == 0) return 0;
     if (sconf_dwconv_window_fwd(x, w, bias, y, B, Ti, Fi, C, stream)) { SCONF_LAUNCH_OK("sconf_sub_dwconv_fwd"); return 0; }
     const LaunchGeo g = geo_for(C, B, (long)To * Fo, 16384);
@@ -614,7 +611,7 @@ SCONF_API int sconf_sub_dwconv_bwd(const void* dout, const float* w, const void*
                                    float* dpre_colsum, void* workspace, int64_t workspace_bytes, int64_t B, int64_t Ti, int64_t Fi,
                                    int64_t C, hipStream_t stream) {
     SUB_REQ("sconf_sub_dwconv_bwd");
-    const int To = (int)((Ti - 1) / 2 + 1), Fo = (int)((Fi - 1) / 2 + 1);
+    const int To = conv_out(Ti), Fo = conv_out(Fi);
     if (B * Ti * Fi == 0) return 0;
     const DwBwdGeo q = dwconv_bwd_geo(B, Ti, Fi, C);
     SCONF_REQUIRE(C / q.cw <= 256, "sconf_sub_dwconv_bwd: C too large");
@@ -636,7 +633,7 @@ SCONF_API int sconf_sub_dwconv_bwd(const void* dout, const float* w, const void*
 SCONF_API int sconf_sub_conv0_bwd(const void* dpre0, const void* x, int x_dtype, float* dw, float* dbias,
                                   int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     SUB_REQ("sconf_sub_conv0_bwd");
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1);
+    const int T2 = conv_out(T), F2 = conv_out(F);
     if (B * T2 * F2 == 0) return 0;
     const LaunchGeo g = geo_for(C, B, (long)T2 * F2, 1024);
     if (x_dtype == SCONF_F32) hipLaunchKernelGGL((conv3x3s2_bwd_weight_kernel<false, float>), g.grid, dim3(g.threads), 0, stream, (const bf16*)dpre0, x, dw, dbias, (int)T, (int)F, (int)C, T2, F2, g.PL, g.iters);
@@ -666,21 +663,16 @@ SCONF_API int sconf_sub_stage01_fwd(const void* x, int x_dtype, const float* w0,
                                     void* d1, int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     SCONF_REQUIRE(C % 4 == 0 && C / 4 <= 256, "sconf_sub_stage01_fwd: C must be a multiple of 4 and <= 1024");
     SCONF_REQUIRE(B <= 65535 && F <= 1024, "sconf_sub_stage01_fwd: B <= 65535 and F <= 1024");
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
+    const int T2 = conv_out(T), F2 = conv_out(F), T4 = conv_out(T2), F4 = conv_out(F2);
     if (B * T4 * F4 == 0) return 0;
     if (sconf_stage01_fwd_mfma(x, x_dtype, w0, b0, wd, bd, d1, B, F, T, C, stream)) { SCONF_LAUNCH_OK("sconf_sub_stage01_fwd"); return 0; }
-    long target = 4096;
-    if (const char* e = getenv("SCONF_SUB_FWD_BLOCKS")) target = atol(e);                       // tuning
+    const long target = env_long("SCONF_SUB_FWD_BLOCKS", 4096);                                 // tuning
     const int rpb = std::max(1, (int)cdiv((long)T4 * B, target));
     dim3 grid(cdiv(T4, rpb), (unsigned)B), block(512);           // 8 waves: two workgroups (LDS-limited) fill a CU's 16 wave slots
     const size_t sh = (size_t)7 * F * 4 + (size_t)3 * F2 * C * 2;
     SCONF_REQUIRE(sh <= 150 * 1024, "sconf_sub_stage01_fwd: the 3-row activation window (%ld B) does not fit LDS", (long)sh);
     static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)stage01_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void*)stage01_fwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
+    lds_limit_once(attr_set, {(const void*)stage01_fwd_kernel<float>, (const void*)stage01_fwd_kernel<bf16>}, 150 * 1024);
     if (x_dtype == SCONF_F32) hipLaunchKernelGGL((stage01_fwd_kernel<float>), grid, block, sh, stream, (const float*)x, w0, b0, wd, bd, (bf16*)d1, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb);
     else hipLaunchKernelGGL((stage01_fwd_kernel<bf16>), grid, block, sh, stream, (const bf16*)x, w0, b0, wd, bd, (bf16*)d1, (int)F, (int)T, (int)C, T2, F2, T4, F4, rpb);
     SCONF_LAUNCH_OK("sconf_sub_stage01_fwd");
@@ -700,7 +692,7 @@ SCONF_API int sconf_sub_stage01_bwd(const void* dd1, const void* x, int x_dtype,
                                     int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
     SCONF_REQUIRE(C % 4 == 0 && C / 4 <= 256, "sconf_sub_stage01_bwd: C must be a multiple of 4 and <= 1024");
     SCONF_REQUIRE(B <= 65535 && F <= 1024, "sconf_sub_stage01_bwd: B <= 65535 and F <= 1024");
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
+    const int T2 = conv_out(T), F2 = conv_out(F), T4 = conv_out(T2), F4 = conv_out(F2);
     if (B * T4 * F4 == 0) return 0;
     const int mf = sconf_stage01_bwd_mfma(dd1, x, x_dtype, w0, b0, wd, dw0, db0, dwd, dbd, workspace, workspace_bytes, B, F, T, C, stream);
     if (mf < 0) return 1;                                      // (error already set)

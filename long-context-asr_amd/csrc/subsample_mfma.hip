@@ -22,24 +22,20 @@
 // launch the kernels always had; wider subsamplers (the paper's 4x models: C = d_model = 768) need the split because neither the
 // forward's 3-row window (3 (F/4 + 2) (4 C + 128) bytes: 211 KB at C = 768, F = 80) nor the backward's dd1 image fits LDS.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 constexpr int PK = 16;                  // im2col columns per position (32 bytes)
 constexpr int PPOS = 64;                // positions per conv0 row image (two 32-row MFMA blocks)
 constexpr int PATCH_BYTES = (PPOS + 1) * PK * 2;   // + one overrun row: the transposed reads of the backward touch row 64
 
 __device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2_t t = {(bf16)a, (bf16)b};
+    bf16x2 t = {(bf16)a, (bf16)b};
     return __builtin_bit_cast(unsigned, t);
 }
 __device__ __forceinline__ float dot2(unsigned a, unsigned b, float c) {
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), c, false);
 }
-__device__ __forceinline__ int acc_pos(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // One conv0 row t2 of the im2col image, entry (pos, column pair kp): fetched from global memory (clamped, unconditional loads;
 // the zero padding and the rows outside [0,T2) are applied as selects) - fetched one row AHEAD into registers, stored later.
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_fwd_mfma_kern
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, wf[u], acc, 0, 0, 0);       // pre0[pos][c], bias included
 #pragma unroll
                 for (int g = 0; g < 8; ++g) {              // 8 pairs of adjacent positions per lane
-                    const int f2 = blk * 32 + acc_pos(2 * g, hh), q = (f2 + 2) >> 1;
+                    const int f2 = blk * 32 + acc_row(2 * g, hh), q = (f2 + 2) >> 1;
                     if (q < NPAIR)                          // positions >= F2 give exactly 0 (their patch rows are zero): the right padding
                         *reinterpret_cast<unsigned*>(arow + q * QS + c * 4) = pack2(siluf_(acc[2 * g]), siluf_(acc[2 * g + 1]));
                 }
@@ -344,7 +340,7 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
     // tap reads need neither clamps nor selects.
     for (int i = tid; i < 3 * GSLOT / 4; i += 512) *reinterpret_cast<unsigned*>(gimg + i * 4) = 0u;
     __syncthreads();                                     // before any wave's DMA can land in a slot another wave is still zeroing
-    const unsigned lds_g = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)gimg);
+    const unsigned lds_g = __builtin_amdgcn_readfirstlane(lds_addr(gimg));
     const int gseg = Cl / 8, gchunks = F4 * gseg;         // 16-byte pieces per segment / per row
     auto gissue = [&](int to) {
         if (to < 0 || to >= T4) return;                                        // uniform
@@ -352,11 +348,7 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
         const unsigned dst = lds_g + (unsigned)((to & 1) * GSLOT) + (unsigned)__builtin_amdgcn_readfirstlane(tid & ~63) * 16u;
         for (int i = 0; i * 512 < gchunks; ++i) {
             const int ch = tid + 512 * i;
-            if (ch < gchunks) {                                                // lanes past the row stay out (the zero bins follow it)
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src + (long)(ch / gseg) * C + (ch % gseg) * 8), "s"(dst + (unsigned)(i * 512 * 16)) : "memory");
-            }
+            if (ch < gchunks) dma16_asm(src + (long)(ch / gseg) * C + (ch % gseg) * 8, dst + (unsigned)(i * 512 * 16));   // lanes past the row stay out (the zero bins follow it)
         }
     };
 
@@ -366,7 +358,7 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
     gissue(r0 >> 1);
     pe.store(patch, tid);
     pe.fetch(xb, F, T, F2, T2, r0 + 1, tid);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
     for (int t2 = r0; t2 < r1; ++t2) {
         const int buf = (t2 - r0) & 1;
@@ -427,14 +419,13 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
                 }
                 // dW0^T += patch^T . dP: A = transposed read of the im2col rows (k on the MFMA rows), B = the packed accumulator
                 {
-                    typedef __attribute__((address_space(3))) bf16x4* lds_p;
                     const int i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3, G = (lane >> 4) & 1;
                     const char* tb = pcur + (blk * 32 + 4 * hh + q4) * (PK * 2) + G * 32 + (p4 >> 1) * 16 + (p4 & 1) * 8;
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
                         if (blk * 32 + 16 * half >= F2) break;
-                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(tb + (16 * half) * (PK * 2)));
-                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(tb + (16 * half + 8) * (PK * 2)));
+                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(tb + (16 * half) * (PK * 2)));
+                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p4)(tb + (16 * half + 8) * (PK * 2)));
                         const bf16x8 at = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                         const uint4 bw = make_uint4(dpk[4 * half], dpk[4 * half + 1], dpk[4 * half + 2], dpk[4 * half + 3]);
                         aw0[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, __builtin_bit_cast(bf16x8, bw), aw0[u], 0, 0, 0);
@@ -444,10 +435,10 @@ __global__ __launch_bounds__(512, (NCB == 1 ? 4 : 2)) void stage01_bwd_mfma_kern
         }
         if (t2 + 1 < r1) pe.store(patch + (buf ^ 1) * PATCH_BYTES, tid);
         pe = pe2;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the dd1 row issued at the top of this (even) row has landed
+        wait_vm<0>();      // the dd1 row issued at the top of this (even) row has landed
         __syncthreads();
     }
-    // ---- results: dW0^T rows k = acc_pos(r, hh): 0..3 / 8 / 9 (= db0) for hh = 0, 4..7 for hh = 1; depthwise sums over both halves
+    // ---- results: dW0^T rows k = acc_row(r, hh): 0..3 / 8 / 9 (= db0) for hh = 0, 4..7 for hh = 1; depthwise sums over both halves
 #pragma unroll
     for (int u = 0; u < NCB; ++u) {
         if (wave + 8 * u >= ncb) break;
@@ -474,9 +465,9 @@ constexpr size_t FWD_LDS_MAX = 160 * 1024, BWD_LDS_MAX = 80 * 1024;             
 // wave idles while another does a second block, as with 384 = 12 blocks) and small enough an LDS image for two workgroups per CU in the
 // forward as well; measured against 2 x 384 at C = 768 in DESIGN.md section 7.  The last slab may be narrower (576 = 256 + 256 + 64).
 static int stage01_slab_channels(long F, long C, bool bwd) {
-    const int F2 = (int)((F - 1) / 2 + 1), F4 = (F2 - 1) / 2 + 1;
+    const int F2 = conv_out(F), F4 = conv_out(F2);
     if (C <= 0 || C % 32 != 0 || C > 1024 || F2 > PPOS) return 0;
-    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return 0;                   // A/B switch
+    if (sub_mfma_off()) return 0;                   // A/B switch
     auto fits = [&](long cs) { return bwd ? stage01_bwd_lds(F4, cs) <= BWD_LDS_MAX : stage01_fwd_lds(F2, cs) <= FWD_LDS_MAX; };
     if (C <= 512) return fits(C) ? (int)C : 0;
     long cs = 256;
@@ -493,17 +484,15 @@ int stage01_mfma_slabs(int64_t F, int64_t C, int bwd) {
 // returns 1 if the MFMA kernels took the problem, 0 if the caller should use the VALU kernels of subsample.hip
 int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const float* b0, const float* wd, const float* bd, void* d1,
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
+    const int T2 = conv_out(T), F2 = conv_out(F), T4 = conv_out(T2), F4 = conv_out(F2);
     const int Cs = stage01_slab_channels(F, C, false);
     if (!Cs) return 0;
     const size_t sh = stage01_fwd_lds(F2, Cs);
-    long target = 4096;
-    if (const char* e = getenv("SCONF_SUB_FWD_BLOCKS")) target = atol(e);                       // tuning
+    const long target = env_long("SCONF_SUB_FWD_BLOCKS", 4096);                                 // tuning
     const int rpb = std::max(1, (int)cdiv((long)T4 * B, target));
     dim3 grid(cdiv(T4, rpb), (unsigned)B, (unsigned)cdiv(C, (long)Cs)), block(512);
 #define LF(TX, NCB_) do { \
-        static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_fwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FWD_LDS_MAX); attr = true; } \
+        static bool attr = false; lds_limit_once(attr, {(const void*)stage01_fwd_mfma_kernel<TX, NCB_>}, FWD_LDS_MAX); \
         hipLaunchKernelGGL((stage01_fwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, bd, (bf16*)d1, (int)F, (int)T, (int)C, Cs, T2, F2, T4, F4, rpb); } while (0)
     if (x_dtype == SCONF_F32) { if (Cs <= 256) LF(float, 1); else LF(float, 2); }
     else                      { if (Cs <= 256) LF(bf16, 1); else LF(bf16, 2); }
@@ -513,12 +502,11 @@ int sconf_stage01_fwd_mfma(const void* x, int x_dtype, const float* w0, const fl
 
 // whether the MFMA backward takes this shape, and its launch geometry
 static bool stage01_bwd_mfma_geo(long B, long F, long T, long C, dim3& grid, size_t& sh, int& rpb, int& Cs) {
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), F4 = (F2 - 1) / 2 + 1;
+    const int T2 = conv_out(T), F2 = conv_out(F), F4 = conv_out(F2);
     Cs = stage01_slab_channels(F, C, true);
     if (!Cs) return false;
     sh = stage01_bwd_lds(F4, Cs);
-    long target = 2048;
-    if (const char* e = getenv("SCONF_SUB_BWD_BLOCKS")) target = atol(e);                       // tuning
+    const long target = env_long("SCONF_SUB_BWD_BLOCKS", 2048);                                 // tuning
     rpb = std::max(2, (int)cdiv((long)T2 * B, target));
     rpb += rpb & 1;                                                                              // even: a block starts on an even conv0 row
     grid = dim3(cdiv(T2, rpb), (unsigned)B, (unsigned)cdiv(C, (long)Cs));
@@ -536,7 +524,7 @@ int64_t stage01_bwd_mfma_workspace(int64_t B, int64_t F, int64_t T, int64_t C) {
 int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const float* w0, const float* b0, const float* wd,
                            float* dw0, float* db0, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
                            int64_t B, int64_t F, int64_t T, int64_t C, hipStream_t stream) {
-    const int T2 = (int)((T - 1) / 2 + 1), F2 = (int)((F - 1) / 2 + 1), T4 = (T2 - 1) / 2 + 1, F4 = (F2 - 1) / 2 + 1;
+    const int T2 = conv_out(T), F2 = conv_out(F), T4 = conv_out(T2), F4 = conv_out(F2);
     dim3 grid; size_t sh; int rpb, Cs;
     if (!stage01_bwd_mfma_geo(B, F, T, C, grid, sh, rpb, Cs)) return 0;
     const dim3 block(512);
@@ -545,7 +533,7 @@ int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const fl
     float* sl = det_begin<float>(workspace, workspace_bytes, rows, dst, stream);
     if (!sl) { sconf_set_error("sconf_sub_stage01_bwd: needs %ld bytes of workspace (sconf_sub_stage01_bwd_workspace)", rows * dst * 4); return -1; }
 #define LB(TX, NCB_) do { \
-        if (sh > 64 * 1024) { static bool attr = false; if (!attr) { (void)hipFuncSetAttribute((const void*)stage01_bwd_mfma_kernel<TX, NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_MAX); attr = true; } } \
+        if (sh > 64 * 1024) { static bool attr = false; lds_limit_once(attr, {(const void*)stage01_bwd_mfma_kernel<TX, NCB_>}, BWD_LDS_MAX); } \
         hipLaunchKernelGGL((stage01_bwd_mfma_kernel<TX, NCB_>), grid, block, sh, stream, (const TX*)x, w0, b0, wd, (const bf16*)dd1, sl, sl + 9 * C, sl + 10 * C, sl + 19 * C, (int)F, (int)T, (int)C, Cs, T2, F2, T4, F4, rpb, dst); } while (0)
     if (x_dtype == SCONF_F32) { if (Cs <= 256) LB(float, 1); else LB(float, 2); }
     else                      { if (Cs <= 256) LB(bf16, 1); else LB(bf16, 2); }
@@ -555,18 +543,16 @@ int sconf_stage01_bwd_mfma(const void* dd1, const void* x, int x_dtype, const fl
 }
 
 int sconf_dwconv_window_fwd(const void* x, const float* w, const float* bias, void* y, int64_t B, int64_t Ti, int64_t Fi, int64_t C, hipStream_t stream) {
-    const int To = (int)((Ti - 1) / 2 + 1), Fo = (int)((Fi - 1) / 2 + 1);
+    const int To = conv_out(Ti), Fo = conv_out(Fi);
     if (C % 32 != 0 || C > 512 || ((Fi + 1) / 2) * (C / 8) > 1024) return 0;
-    if (const char* e = getenv("SCONF_SUB_MFMA")) if (e[0] == '0') return 0;                   // A/B switch (shared with the fused stage)
+    if (sub_mfma_off()) return 0;                   // A/B switch (shared with the fused stage)
     const size_t sh = 3 * (size_t)(Fi / 2 + 2) * (4 * C + 128);
     if (sh > 160 * 1024) return 0;
-    long target = 4096;
-    if (const char* e = getenv("SCONF_SUB_FWD_BLOCKS")) target = atol(e);
+    const long target = env_long("SCONF_SUB_FWD_BLOCKS", 4096);
     const int rpb = std::max(1, (int)cdiv((long)To * B, target));
     dim3 grid(cdiv(To, rpb), (unsigned)B), block(512);
 #define LW(NCB_) do { \
-        static bool attr = false; \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)dwconv_window_fwd_kernel<NCB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
+        static bool attr = false; lds_limit_once(attr, {(const void*)dwconv_window_fwd_kernel<NCB_>}, 160 * 1024); \
         hipLaunchKernelGGL((dwconv_window_fwd_kernel<NCB_>), grid, block, sh, stream, (const bf16*)x, w, bias, (bf16*)y, (int)Ti, (int)Fi, (int)C, To, Fo, rpb); } while (0)
     if (C <= 256) LW(1); else LW(2);
 #undef LW

@@ -288,18 +288,18 @@ def test_ctc_grid_cap_of_the_gather_and_rows_per_workgroup_of_the_fused_backward
 
 # ------------------------------------------------------------------------------------------- elementwise, grid-stride loops
 # Grid caps of the entry points below (workgroups; no query exposes them, so each case is sized at >= 2.5 x the capped grid's reach
-# and names the launcher's line under long-context-asr_amd/csrc/):
-CAP_CAST = 4096            # elementwise.hip:320  sconf_cast, 256 threads x 8 elements
-CAP_AFFINE = 8192          # convmod.hip:385      sconf_affine_silu_fwd, 256 threads x 8 elements
-CAP_MASK = 8192            # elementwise.hip:505  sconf_mask_rows, 256 threads x 4 elements
-CAP_ROT_INPLACE = 16384    # elementwise.hip:355  sconf_rotary_inplace, 256 threads, one (row, q|k, head, 8 pairs) each
-CAP_ROT_QKV = 8192         # elementwise.hip:368  sconf_rotary_qkv, 256 threads, one (row, head, 8 pairs) each
-CAP_ROWDOT = 65536         # elementwise.hip:422  sconf_rowdot, 4 rows (one per wave)
-CAP_OVERLAP = 16384        # infer.hip:92, 103    sconf_overlap_add_exp / sconf_overlap_finalize, 256 threads x 4 columns
-CAP_SILU_T = 8192          # subsample.hip:665    sconf_sub_silu_transpose, one row per workgroup
-CAP_SUMSQ = 2048           # optim.hip:87         sconf_sumsq, 256 threads x 4 elements
-CAP_MADGRAD = 4096         # optim.hip:115        sconf_madgrad_step, 256 threads x 4 elements
-CAP_CTC_GATHER = 65536     # ctc.hip:572          ctc_gather_kernel, one frame per workgroup
+# and names the launcher, file and function, under long-context-asr_amd/csrc/):
+CAP_CAST = 4096            # elementwise.hip: sconf_cast, 256 threads x 8 elements
+CAP_AFFINE = 8192          # convmod.hip:     sconf_affine_silu_fwd, 256 threads x 8 elements
+CAP_MASK = 8192            # elementwise.hip: sconf_mask_rows, 256 threads x 4 elements
+CAP_ROT_INPLACE = 16384    # elementwise.hip: sconf_rotary_inplace, 256 threads, one (row, q|k, head, 8 pairs) each
+CAP_ROT_QKV = 8192         # elementwise.hip: sconf_rotary_qkv, 256 threads, one (row, head, 8 pairs) each
+CAP_ROWDOT = 65536         # elementwise.hip: sconf_rowdot, 4 rows (one per wave)
+CAP_OVERLAP = 16384        # infer.hip:       sconf_overlap_add_exp / sconf_overlap_finalize, 256 threads x 4 columns
+CAP_SILU_T = 8192          # subsample.hip:   sconf_sub_silu_transpose, one row per workgroup
+CAP_SUMSQ = 2048           # optim.hip:       sconf_sumsq, 256 threads x 4 elements
+CAP_MADGRAD = 4096         # optim.hip:       sconf_madgrad_step, 256 threads x 4 elements
+CAP_CTC_GATHER = 65536     # ctc.hip:         ctc_fwd_impl launching ctc_gather_kernel, one frame per workgroup
 
 
 def _blocks(n, reach, rows=4096):
