@@ -25,6 +25,20 @@
 //        row included) makes that true for all waves before any L_(P+1) read.  Issue phases: A0, B0 of K-tile s+2 in
 //        (s, q2), (s, q3); B1, A1 of K-tile s+1 in (s, q0), (s, q1); read phases: A0/B0 q0, B1 q1, A1 q2 - always >= 5
 //        phases after the issue.
+//   DMA issue (dma_voff, Cursor below): `buffer_load_dwordx4 ... offen lds` from inline asm (gfx950.h dma_pieces / dma_piece), one
+//        statement per half-tile.  Per lane ONE loop-invariant 32-bit offset per operand; the descriptor (based at the K-tile's corner
+//        of the operand, num_records = what the operand has left from there), the piece / half steps and the LDS destination (M0) are
+//        scalar.  What the asm form changes for the hazards above: nothing in the ORDER - the statements clobber "memory", so the
+//        compiler moves no LDS read and no epilogue load or store across an issue or a wait, and every issue sits where the builtin
+//        sat - but the compiler no longer counts these loads: vmcnt is in order and shared, the loop holds no vector-memory
+//        operation of the compiler's own, and the epilogue's loads are issued after the item's last DMA, so a wait the compiler
+//        emits for them also retires the older DMA (it over-waits, never under-waits).  M0 is saved and restored inside each
+//        statement; SCC is named as clobbered.
+//   Tail  past the workgroup's last item the cursor is invalid: nothing is issued and the wait drains (vmcnt(0)).  The test is one
+//        scalar compare and branch per phase.  (A zero-record descriptor would turn the issue into a no-op with the same vmcnt
+//        accounting, but it writes zeros through the LDS-DMA path into the next K-tile's images while the other wave row may still
+//        be two barriers behind: safe by the WAR rule above, yet it buys one branch and costs 8 zero-fill pieces per K-tile of the
+//        tail - not taken.)
 #ifdef SCONF_GEMM_STAMP
 #define SCONF_STAMPS                 // gfx950.h: STAMP_DECL / STAMP are live in this file
 #endif
@@ -54,39 +68,44 @@ __device__ __forceinline__ int swz_a(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int swz_b(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }
 __device__ __forceinline__ int swz_b1n(int row) { return ((row >> 1) & 1) | (((row >> 2) & 3) << 1); }   // 64-row B1 image
 
-// per-lane source byte offsets (relative to the half-tile's wave-uniform base) of the DMA pieces of each half
-template <bool KS, bool BOP, int JH> struct DmaOffs {
-    unsigned off[2][2];
-    // rot (B operand of the 256-wide tile only): the wave's lo / hi column runs are d and d + 64 of ONE head (tile = 2 heads of 128),
-    // so that a lane holds both partners of the rotary rotation: wave wc takes head wc >> 1, d in [32 (wc & 1), +32) | that + 64.
-    __device__ __forceinline__ void set(long ld, int tid, bool rot = false) {
-        constexpr int WC = 32 + 16 * JH;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int c = tid + 512 * i;
-                if (!KS) {
-                    const int row = c >> 3, pos = c & 7;
-                    int kc, mrow;
-                    if (!BOP)              { kc = pos ^ swz_a(row); mrow = 128 * h + row; }
-                    else if (h == 0)       { kc = pos ^ swz_b(row); mrow = rot ? 128 * (row >> 6) + 32 * ((row >> 5) & 1) + (row & 31) : WC * (row >> 5) + (row & 31); }
-                    else if (JH == 2)      { kc = pos ^ swz_b(row); mrow = rot ? 128 * (row >> 6) + 32 * ((row >> 5) & 1) + 64 + (row & 31) : WC * (row >> 5) + 32 + (row & 31); }
-                    else                   { kc = pos ^ swz_b1n(row & 63); mrow = WC * ((row & 63) >> 4) + 32 + (row & 15); }
-                    off[h][i] = (unsigned)(((long)mrow * ld + kc * 8) * 2);
-                } else {
-                    const int kr = c >> 4, pos = c & 15, rc = pos ^ swz_strided(kr);
-                    off[h][i] = (unsigned)(((long)kr * ld + 128 * h + rc * 8) * 2);
-                }
-            }
+// ---- LDS-DMA prefetch: one buffer descriptor per operand, everything but one 32-bit offset per lane in scalar registers ----
+// A half-tile image is 2 pieces of 512 lanes x 16 B (B1 of the 192-wide tile: 1); piece i of half h reads, for thread tid,
+// chunk c = tid + 512 i.  The per-lane source offset of piece 0 of half 0 (dma_voff) is the only per-lane part of the address:
+//   K-contiguous (row = c >> 3, 8 chunks of 16 B per row):
+//     A           mrow = 128 h + row, swizzle swz_a(row) = (row >> 1) & 7:   piece +64 rows, half +128 rows - bits 1..3 of row untouched;
+//     B0 / B1     mrow = WC (row >> 5) + 32 h + (row & 31), swz_b(row) uses bits 1, 3, 4:   piece +64 image rows = +2 WC operand rows, half +32;
+//     B, rotary   mrow = 128 (row >> 6) + 32 ((row >> 5) & 1) + 64 h + (row & 31):   piece +128 rows, half +64;
+//     B1 of the 192-wide tile is a 64-row image with its own row map and swizzle (swz_b1n): a second per-lane offset, one piece;
+//   K-strided (kr = c >> 4, 16 chunks per k-row): kr ld + 128 h + 8 (pos ^ swz_strided(kr)); swz_strided uses bits 0, 1, 3 of kr:
+//     piece +32 k-rows, half +256 B.
+// Every step is wave-uniform and leaves the XOR swizzle alone, so it lives in an SGPR (the piece step goes through dma_pieces'
+// soffset, the half step is the soffset it starts from).  The LDS destination is wave-uniform too: par * BUF + image * HT +
+// wave * 1024 (+ 8192 for the second piece), written to M0 from SGPRs.
+template <bool KS, bool BOP, int JH> __device__ __forceinline__ unsigned dma_voff(long ld, int tid, bool rot = false, bool narrow_b1 = false) {
+    constexpr int WC = 32 + 16 * JH;
+    if (KS) {
+        const int kr = tid >> 4, pos = tid & 15, rc = pos ^ swz_strided(kr);
+        return (unsigned)(((long)kr * ld + rc * 8) * 2);
     }
-};
-template <int NP>
-__device__ __forceinline__ void dma_half(const char* base, const unsigned (&off)[2], char* dst, int tid) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-        __builtin_amdgcn_global_load_lds((gptr)(base + off[i]), (lptr)(dst + ((tid & ~63) + 512 * i) * 16), 16, 0, 0);
+    const int row = tid >> 3, pos = tid & 7;                       // row < 64
+    int kc, mrow;
+    if (!BOP)           { kc = pos ^ swz_a(row); mrow = row; }
+    else if (narrow_b1) { kc = pos ^ swz_b1n(row); mrow = WC * (row >> 4) + 32 + (row & 15); }
+    else                { kc = pos ^ swz_b(row); mrow = rot ? 32 * (row >> 5) + (row & 31) : WC * (row >> 5) + (row & 31); }
+    return (unsigned)(((long)mrow * ld + kc * 8) * 2);
 }
+// wave-uniform byte steps of one operand's images: second piece of a half, second half (A: twice the piece step; K-strided: 256 B -
+// derived at the issue, not kept in registers of their own)
+template <bool KS, bool BOP, int JH> struct DmaSteps {
+    unsigned piece, bhalf;
+    __device__ __forceinline__ void set(long ld, bool rot = false) {
+        constexpr int WC = 32 + 16 * JH;
+        if (KS)        { piece = (unsigned)(32 * ld * 2); bhalf = 256; }
+        else if (!BOP) { piece = (unsigned)(64 * ld * 2); bhalf = 0; }
+        else           { piece = (unsigned)((rot ? 128 : 2 * WC) * ld * 2); bhalf = (unsigned)((rot ? 64 : 32) * ld * 2); }
+    }
+    __device__ __forceinline__ unsigned half() const { return KS ? 256u : !BOP ? 2 * piece : bhalf; }
+};
 
 // Transposed LDS read as inline asm.  Through the builtin, hipcc puts an unconditional `s_waitcnt vmcnt(0)` in front of the
 // reads (it cannot tell them from the in-flight LDS-DMA destinations), which drains the whole prefetch pipeline twice per
@@ -165,16 +184,42 @@ __device__ __forceinline__ Item item_coords(const GemmParams& p, const Sched& sc
     w.nkt = (min(p.K, w.kbeg + p.k_per_split) - w.kbeg) / TK;
     return w;
 }
-// position in the workgroup's stream of K-tiles (all wave-uniform)
-struct Cursor {
-    int v, kt, par; bool valid; Item it;
-    __device__ __forceinline__ void advance(const GemmParams& p, const Sched& sc) {
-        par ^= 1;
-        if (++kt < it.nkt) return;
-        kt = 0; v += gridDim.x;
-        if (v < sc.total) it = item_coords(p, sc, v); else valid = false;
+// One past the last byte of each operand and the K-tile steps of the prefetch stream (wave-uniform, set once per launch).
+template <bool KS> struct DmaGeom {
+    const char* aend; const char* bend; long astep, bstep;
+    __device__ __forceinline__ void set(const GemmParams& p) {
+        aend = reinterpret_cast<const char*>(p.A) + (KS ? (long)(p.K - 1) * p.lda + p.M : (long)(p.M - 1) * p.lda + p.K) * 2;
+        bend = reinterpret_cast<const char*>(p.B) + (KS ? (long)(p.K - 1) * p.ldb + p.N : (long)(p.N - 1) * p.ldb + p.K) * 2;
+        astep = KS ? TK * p.lda * 2 : TK * 2; bstep = KS ? TK * p.ldb * 2 : TK * 2;
     }
 };
+// Position in the workgroup's stream of K-tiles (all wave-uniform, i.e. SGPRs; `valid` is an int so that it is tested as a scalar, not
+// as a lane mask).  pa / pb point at the K-tile's corner of each operand: the bases of the buffer descriptors the DMA is issued
+// through, whose num_records is what the operand has left from there (an indexing error reads zeros, not memory past the tensor).
+// They are REBASED with 64-bit arithmetic, per work item by seek() (the stream's only multiplies) and per K-tile by a scalar add in
+// advance(), so that what is left for the 32-bit offset fields is one pair of half-tiles: operands of any size, and K-strided items
+// whose k-range times ld passes 4 GiB, stay on this kernel.
+template <bool KS> struct Cursor {
+    int v, kt, par, valid; Item it;
+    const char* pa; const char* pb;
+    __device__ __forceinline__ void seek(const GemmParams& p) {
+        pa = reinterpret_cast<const char*>(p.A) + (KS ? (long)it.kbeg * p.lda + it.m0 : (long)it.m0 * p.lda + it.kbeg) * 2;
+        pb = reinterpret_cast<const char*>(p.B) + (KS ? (long)it.kbeg * p.ldb + it.n0 : (long)it.n0 * p.ldb + it.kbeg) * 2;
+    }
+    __device__ __forceinline__ void advance(const GemmParams& p, const Sched& sc, const DmaGeom<KS>& g) {
+        par ^= 1;
+        if (++kt < it.nkt) { pa += g.astep; pb += g.bstep; return; }
+        kt = 0; v += gridDim.x;
+        if (v < sc.total) { it = item_coords(p, sc, v); seek(p); } else valid = 0;
+    }
+};
+// descriptor over [base, end), num_records clamped to 4 GiB - 1 by the high word of the distance.  The high word passes through
+// tie_s: written as a plain 64-bit comparison it becomes v_cmp_lt_u64 (there is no scalar one) - two VALU instructions per issue.
+__device__ __forceinline__ srd_t dma_srd(const char* base, const char* end) {
+    const unsigned long left = (unsigned long)(end - base);
+    const unsigned hi = tie_s((unsigned)(left >> 32));
+    return make_srd_uniform(base, hi ? 0xffffffffL : (long)(unsigned)left);
+}
 
 // Epilogue of one work item for one wave (ACT and the presence of a residual fixed at compile time).  All loads are issued
 // before the stores they could queue behind: the bias run once, the aux tile (bf16) per half of 4 row blocks, the residual
@@ -189,7 +234,7 @@ __device__ __forceinline__ void epilogue256(const GemmParams& p, const f32x4 (&a
     constexpr bool SMB = ACT == SCONF_ACT_SMAXBWD;    // softmax backward: per-row scalar in, column sums out
     const int g = lane >> 4, mbase = it.m0 + 64 * wr + (lane & 15);
     if constexpr (ROT) {
-        // qkv projection with the rotary rotation: with the rot row permutation (DmaOffs::set) the lane's lo run is (head, d0 .. d0 + 7)
+        // qkv projection with the rotary rotation: with the rot row permutation (dma_voff) the lane's lo run is (head, d0 .. d0 + 7)
         // and its hi run (head, d0 + 64 ..): out[d] = x[d] cos - x[d + 64] sin, out[d + 64] = x[d + 64] cos + x[d] sin
         // (apply_rotary_pos_emb, rotary_emb.py:61-73) on the f32 accumulators - one bf16 rounding instead of two.  Tiles past
         // rot_cols (the v block) are stored as they are.  cos / sin of the next row block are requested before this one is stored.
@@ -465,20 +510,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     if ((int)blockIdx.x >= sc.total) return;
 
     const int ekind = __builtin_amdgcn_readfirstlane(epilogue_kind(p));
-    DmaOffs<KS, false, JH> oa; DmaOffs<KS, true, JH> ob;
-    oa.set(p.lda, tid); ob.set(p.ldb, tid, !KS && p.rot_cos != nullptr);
-    auto issue_a = [&](const Cursor& c, int h) {
+    // LDS-DMA prefetch (dma_voff above): per lane one offset per operand; descriptor, steps and LDS destination are scalar
+    const bool rotb = !KS && p.rot_cos != nullptr;
+    const unsigned va = dma_voff<KS, false, JH>(p.lda, tid), vb = dma_voff<KS, true, JH>(p.ldb, tid, rotb);
+    DmaSteps<KS, false, JH> sa; DmaSteps<KS, true, JH> sb; sa.set(p.lda); sb.set(p.ldb, rotb);
+    DmaGeom<KS> geo; geo.set(p);
+    const unsigned ldsw = lds_addr(smem) + wave * 1024;
+    // the wave's slot in buffer `par`; the image offset is added as a literal at the issue (tie_s: else the compiler hoists one sum per image)
+    auto lds_buf = [&](int par) { return tie_s(ldsw + par * BUF); };
+    auto issue_a = [&](const Cursor<KS>& c, int h) {
         if (!c.valid) return;
-        const long k0 = c.it.kbeg + c.kt * TK;
-        const char* base = reinterpret_cast<const char*>(p.A) + (KS ? k0 * p.lda + c.it.m0 : (long)c.it.m0 * p.lda + k0) * 2;
-        dma_half<2>(base, oa.off[h], smem + c.par * BUF + h * HT, tid);
+        dma_pieces<2, 8192>(dma_srd(c.pa, geo.aend), va, h * sa.half(), sa.piece, lds_buf(c.par) + h * HT);
     };
-    auto issue_b = [&](const Cursor& c, int h) {
+    auto issue_b = [&](const Cursor<KS>& c, int h) {
         if (!c.valid) return;
-        const long k0 = c.it.kbeg + c.kt * TK;
-        const char* base = reinterpret_cast<const char*>(p.B) + (KS ? k0 * p.ldb + c.it.n0 : (long)c.it.n0 * p.ldb + k0) * 2;
-        if (h == 0) dma_half<2>(base, ob.off[0], smem + c.par * BUF + 2 * HT, tid);
-        else        dma_half<JH>(base, ob.off[1], smem + c.par * BUF + 3 * HT, tid);
+        dma_pieces<2, 8192>(dma_srd(c.pb, geo.bend), vb, h * sb.half(), sb.piece, lds_buf(c.par) + (2 + h) * HT);
     };
 
     f32x4 acc[2][4][2 + JH];
@@ -489,12 +535,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 2 + JH; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    Cursor pc;                                        // prefetch cursor
-    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = true; pc.it = item_coords(p, sc, pc.v);
+    Cursor<KS> pc;                                    // prefetch cursor
+    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p);
     int cv = pc.v; Item cit = pc.it;                  // compute position
     // prologue: K-tile 0 entirely, A0/B0 of K-tile 1 (the "phases -6 .. -1" of the schedule)
     issue_a(pc, 0); issue_b(pc, 0); issue_b(pc, 1); issue_a(pc, 1);
-    pc.advance(p, sc);
+    pc.advance(p, sc, geo);
     issue_a(pc, 0); issue_b(pc, 0);
     if (pc.valid) wait_window<JH>(true);             // A0, B0 of K-tile 0 have landed
     else wait_vm<4>();
@@ -598,7 +644,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int kk = 0; kk < 2; ++kk) fa[i][kk] = frag_a<KS>(buf + HT, wr, i, kk, lane);
                 }
             }
-            pc.advance(p, sc);
+            pc.advance(p, sc, geo);
             STAMP(6);
             issue_a(pc, 0);
             STAMP(7);
@@ -691,19 +737,22 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
     if ((int)blockIdx.x >= sc.total) return;
 
     const int ekind = __builtin_amdgcn_readfirstlane(epilogue_kind(p));
-    DmaOffs<false, false, JH> oa; DmaOffs<false, true, JH> ob;
-    oa.set(p.lda, tid); ob.set(p.ldb, tid);
-    auto issue_a = [&](const Cursor& c, int h) {
+    constexpr bool KS = false;
+    const unsigned va = dma_voff<KS, false, JH>(p.lda, tid), vb = dma_voff<KS, true, JH>(p.ldb, tid);
+    const unsigned vb1 = dma_voff<KS, true, JH>(p.ldb, tid, false, true);          // the 64-row B1 image: own row map and swizzle
+    DmaSteps<KS, false, JH> sa; DmaSteps<KS, true, JH> sb; sa.set(p.lda); sb.set(p.ldb);
+    DmaGeom<KS> geo; geo.set(p);
+    const unsigned ldsw = lds_addr(smem) + wave * 1024;
+    // the wave's slot in buffer `par`; the image offset is added as a literal at the issue (tie_s: else the compiler hoists one sum per image)
+    auto lds_buf = [&](int par) { return tie_s(ldsw + par * BUF); };
+    auto issue_a = [&](const Cursor<KS>& c, int h) {
         if (!c.valid) return;
-        const long k0 = c.it.kbeg + c.kt * TK;
-        dma_half<2>(reinterpret_cast<const char*>(p.A) + ((long)c.it.m0 * p.lda + k0) * 2, oa.off[h], smem + c.par * BUF + h * HT, tid);
+        dma_pieces<2, 8192>(dma_srd(c.pa, geo.aend), va, h * sa.half(), sa.piece, lds_buf(c.par) + h * HT);
     };
-    auto issue_b = [&](const Cursor& c, int h) {
+    auto issue_b = [&](const Cursor<KS>& c, int h) {
         if (!c.valid) return;
-        const long k0 = c.it.kbeg + c.kt * TK;
-        const char* base = reinterpret_cast<const char*>(p.B) + ((long)c.it.n0 * p.ldb + k0) * 2;
-        if (h == 0) dma_half<2>(base, ob.off[0], smem + c.par * BUF + 2 * HT, tid);
-        else        dma_half<1>(base, ob.off[1], smem + c.par * BUF + 3 * HT, tid);
+        if (h == 0) dma_pieces<2, 8192>(dma_srd(c.pb, geo.bend), vb, 0, sb.piece, lds_buf(c.par) + 2 * HT);
+        else        dma_piece(dma_srd(c.pb, geo.bend), vb1, 0, lds_buf(c.par) + 3 * HT);
     };
 
     f32x4 acc[2][4][3];
@@ -714,12 +763,12 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    Cursor pc;                                        // prefetch cursor: the K-tile whose A0/B0 were issued last
-    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = true; pc.it = item_coords(p, sc, pc.v);
+    Cursor<KS> pc;                                    // prefetch cursor: the K-tile whose A0/B0 were issued last
+    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p);
     int cv = pc.v; Item cit = pc.it;
     // prologue: K-tile 0 entirely, A0/B0 of K-tile 1
     issue_a(pc, 0); issue_b(pc, 0); issue_a(pc, 1); issue_b(pc, 1);
-    pc.advance(p, sc);
+    pc.advance(p, sc, geo);
     issue_a(pc, 0); issue_b(pc, 0);
     if (pc.valid) wait_vm<7>(); else wait_vm<3>();           // A0, B0 of K-tile 0 have landed
     __builtin_amdgcn_s_barrier();
@@ -772,7 +821,7 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_s_barrier();
             // ---- P2 ------------------------------------------------------------------------------------------------
-            pc.advance(p, sc);                          // pc = K-tile s+2
+            pc.advance(p, sc, geo);                          // pc = K-tile s+2
             issue_a(pc, 0); issue_b(pc, 0);
             wait_window<JH>(pc.valid);
             __builtin_amdgcn_s_barrier();
@@ -827,8 +876,13 @@ bool sconf_gemm256_eligible(const GemmParams& p, int layout) {
     if (ks ? (p.act != SCONF_ACT_NONE || p.resid || p.pre)
            : !(p.act == SCONF_ACT_NONE || ((p.act == SCONF_ACT_GELU_DSAVE || p.act == SCONF_ACT_MULAUX) && !p.resid) ||
                (p.act == SCONF_ACT_SMAXBWD && !p.resid && !p.bias && !p.out_f32 && !p.pre && p.splits == 1))) return false;
-    // 32-bit per-lane source offsets relative to a half-tile base
-    if ((ks ? 64 : 256) * p.lda * 2 >= (1L << 32) || (ks ? 64 : 256) * p.ldb * 2 >= (1L << 32)) return false;
+    // The 32-bit offset fields of the LDS-DMA (per-lane voffset + scalar soffset, against a descriptor that the kernel rebases to
+    // the K-tile's corner of the operand with 64-bit arithmetic): the farthest 16 bytes of one K-tile's pair of half-tiles end
+    // (255 ld + 64) * 2 bytes from that corner for a K-contiguous operand (256 rows x 64 k) and (63 ld + 256) * 2 for a K-strided one
+    // (64 k-rows x 256), and num_records is at most 2^32 - 1.  Neither the operand's size nor an item's k-range enters: operands
+    // beyond 4 GiB and K-strided items whose k-range times ld passes 4 GiB stay on this kernel.
+    auto fits32 = [&](long ld) { return (ks ? 63 * ld + 256 : 255 * ld + 64) * 2 <= 0xffffffffL; };
+    if (!fits32(p.lda) || !fits32(p.ldb)) return false;
     const int cus = num_cus();
     const int w = pick_width(p, layout, cus);
     if (!w || (p.act == SCONF_ACT_SMAXBWD && w != 256)) return false;

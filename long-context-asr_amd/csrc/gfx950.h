@@ -24,6 +24,8 @@ __device__ __forceinline__ void wait_lgkm0_barrier() { asm volatile("s_waitcnt l
 // loads waited for) and can neither hoist what is derived from it above the statement nor keep such results live across it.
 template <typename T> __device__ __forceinline__ void tie(T& x) { asm volatile("" : "+v"(x)); }
 __device__ __forceinline__ int opaque(int v) { tie(v); return v; }
+// the same for a wave-uniform value in an SGPR: what is computed from the result stays scalar and is not folded into what produced x
+__device__ __forceinline__ unsigned tie_s(unsigned x) { asm("" : "+s"(x)); return x; }
 template <int NF> __device__ __forceinline__ void pin_frags(bf16x8 (&f)[NF]) {
 #pragma unroll
     for (int i = 0; i < NF; ++i) tie(f[i]);
@@ -70,6 +72,11 @@ __device__ __forceinline__ srd_t make_srd(const void* base, long nbytes) {
     const unsigned nb = __builtin_amdgcn_readfirstlane((unsigned)(nbytes > 0xffffffffL ? 0xffffffffL : nbytes));
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long)hi << 32) | lo), 0, nb, 0x00020000);
 }
+// the same over values that are ALREADY wave-uniform (kernel arguments, scalar loop state): no readfirstlane, so a descriptor that
+// is rebased inside a loop costs SALU only.  A per-lane value here does not compile ("illegal VGPR to SGPR copy").
+__device__ __forceinline__ srd_t make_srd_uniform(const void* base, long nbytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (unsigned)(nbytes > 0xffffffffL ? 0xffffffffL : nbytes), 0x00020000);
+}
 // The descriptor forms open with `s_nop 4`: the descriptor and soff may come straight out of VALU readfirstlanes, and a VALU write
 // of an SGPR needs wait states before a VMEM instruction reads it that the assembler does not insert inside an asm statement.
 // s_add_u32 writes SCC: the multi-piece form names "scc" as a clobber (the single-dword form has no s_add).  Both clobber memory.
@@ -83,6 +90,12 @@ __device__ __forceinline__ void dma_dword(srd_t srd, unsigned voff, unsigned sof
 #define SCONF_DMA_FIRST "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
 #define SCONF_DMA_NEXT  "s_add_u32 m0, m0, %6\n\ts_add_u32 %1, %1, %4\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
 #define SCONF_DMA_LAST  "s_mov_b32 m0, %0"
+// one piece: dma_pieces' first step alone - the same s_nop 4, M0 save / set / s_nop 0 / restore; no s_add, so SCC stays untouched
+__device__ __forceinline__ void dma_piece(srd_t srd, unsigned voff, unsigned soff, unsigned lds_wave_base) {
+    unsigned keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(srd), "s"(soff), "s"(lds_wave_base) : "memory");
+}
 template <int NP, int LSTEP> __device__ __forceinline__ void dma_pieces(srd_t srd, unsigned voff, unsigned soff, unsigned sstep, unsigned lds_wave_base) {
     static_assert(NP == 2 || NP == 4 || NP == 8, "tiles of 2, 4 or 8 pieces per wave");
     unsigned keep;

@@ -12,7 +12,7 @@ lines = ['"Name","Calls","TotalDurationNs","AverageNs","Percentage","MinNs","Max
 for n, c, t, a, mn, mx in rows:
     lines.append(f'"{n}",{c},{t},{a:.1f},{100.0 * t / tot:.4f},{mn},{mx}')
 # family rows: the 256-row NT GEMM kernels exist as one instantiation per epilogue kind; bench.py's roofline line is about the family
-fams = {'gemm256_kernel<false, 2, *> (NT 256x256, all epilogue instantiations)': '14gemm256_kernelILb0ELi2ELi',
+fams = {'gemm256_kernel<false, *> (NT 256x256, all epilogue instantiations)': '14gemm256_kernelILb0ELi',
         'gemm192_kernel<*> (NT 256x192, all epilogue instantiations)': '14gemm192_kernelILi'}
 for label, pat in fams.items():
     sel = [r for r in rows if pat in r[0]]
