@@ -122,7 +122,8 @@ int sconf_softmax_fwd(int mode, const void* x, int x_dtype, void* y, int y_dtype
 int sconf_softmax_bwd(int mode, const void* y, int y_dtype, const void* dy, int dy_dtype, void* dx, int dx_dtype,
                       float* colsum_out, float* workspace, int64_t M, int64_t C, sconf_stream_t stream);
 /* colsum_out (optional, f32 [C], accumulated): column sums of dx = the bias gradient of the Linear that produced the logits, from
- * the same pass; needs `workspace` of sconf_softmax_bwd_workspace(M, C) floats. */
+ * the same pass; needs `workspace` of sconf_softmax_bwd_workspace(M, C) floats.  Summed in a fixed order (per-workgroup sums in the
+ * workspace, then sconf_colsum over them): the same result every run. */
 int64_t sconf_softmax_bwd_workspace(int64_t M, int64_t C);
 
 /* out[n] += alpha * sum_m x[m][n]  (bias gradients).  Summed in a fixed order (the same result every run): workspace of
@@ -140,6 +141,9 @@ int sconf_mask_rows(void* x, int dtype, const int32_t* lengths, int64_t B, int64
  * strides {batch, token, head}; lengths: int32 [B] or NULL; window (-1 = unbounded); lse: f32 (B,H,N).
  * sconf_attn_bwd: delta is f32 scratch of 2*B*H*N floats (the dQ kernel, which runs first, leaves the row statistics of the
  * dK/dV kernel there: -rowsum(dO*O) and -lse*log2(e)). */
+/* Rows at or beyond a sample's length are DEFINED, not skipped: sconf_attn_fwd writes o = 0 and lse = +inf there, sconf_attn_bwd
+ * writes dq = dk = dv = 0 there.  Every element of o, lse, dq, dk, dv is written;
+ * the padding between the tokens and batches of a strided view is never touched. */
 /* Which kernel set the two calls below run (bookkeeping for tests and benchmarks, in the manner of sconf_gemm_variant): 8 = the
  * 8-wave kernels (head_dim 128, N >= 256, views addressable with 32-bit byte offsets), 4 = the 4-wave ones, -1 = unsupported head_dim.
  * token_stride: the largest token stride (elements) among the views passed. */
@@ -181,6 +185,10 @@ int sconf_attn_offset_profile(const void* q, const void* k, const float* lse, fl
 /* Conformer conv module, token-major (convolution.py:103-124; conv1dFunc seam convolution.py:6-22; batchrenorm.py:52-92).
  * The statistics and parameter gradients are summed in a fixed order through the caller's workspace (sizes from the
  * *_workspace queries, in bytes): the same result every run. */
+/* sconf_glu_dwconv_fwd: h is written for every row of (B*N, d), rows t >= lengths[b] included (the convolution sees zeros there:
+ * the taps that reach back into the sample, plus the bias); stats f64 [2][d] = [sum h, sum h^2] is ACCUMULATED: zero it first.
+ * sconf_convmod_bwd: red f64 [2][d] is scratch that must be ZERO on entry (the kernel sums into it and reads it back); bcoef
+ * f32 [3][d] is overwritten; dw is accumulated as [ksize][d]; dg is written for every row. */
 int64_t sconf_glu_dwconv_fwd_workspace(int64_t B, int64_t N, int64_t d);
 int sconf_glu_dwconv_fwd(const void* g, const int32_t* lengths, const float* w, const float* bias, void* h, double* stats,
                          void* workspace, int64_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t ksize,
@@ -234,6 +242,13 @@ int sconf_sub_silu_transpose(int bwd, const void* pre, const void* ds, void* out
  * offs: f64 [2*B*N + B] workspace written by the forward and read by the backward: alpha and beta rows are stored relative to a
  * per-frame offset (kept in f64, together with the f64 nll), which keeps the f32 lattice exact to ~1e-4 at 16384 frames where the
  * plain log-space recursion (and torch's own f32 op) is 24 % off in the gradient. */
+/* What the forward defines: nll, and lpg (and lse of the logits form) for EVERY frame and state of the buffer: the emission of the
+ * state's label inside the sample, 0 at frames t >= input_lengths[b] and states s >= 2 * target_lengths[b] + 1.  UNSPECIFIED after the forward (never written,
+ * never read by the backward): alpha and beta at frames t >= input_lengths[b] and at states s >= 2 * target_lengths[b] + 1, and the
+ * alpha / beta entries of offs for frames t >= input_lengths[b] (the B f64 nll entries at its end are always written).
+ * The backward writes every element of grad / dlogits: 0 at frames t >= input_lengths[b], NaN inside a sample whose nll is not
+ * finite.  The occupancy of a label that occurs in several states of a frame (the blank always does) is summed with f32 atomics in
+ * LDS: grad / dlogits are reproducible to rounding, not bit for bit. */
 int sconf_ctc_fwd(const float* log_probs, const int32_t* targets, const int32_t* input_lengths,
                   const int32_t* target_lengths, float* lpg, float* alpha, float* beta, double* offs, float* nll, int64_t B, int64_t N,
                   int64_t C, int64_t Smax, int blank, sconf_stream_t stream);
@@ -309,6 +324,7 @@ int sconf_mean_f32(const float* x, int64_t B, int64_t R, int64_t T, const int32_
  * padded, target_lengths (B) int32, -1 where a sequence has more than S_cap labels (nothing is written past the buffer).
  * idx (B*N) int32 receives the frame arg-maxes.  GreedyCTCDecoder.forward (lcasr/decoding/greedy.py:19-21) followed by the
  * re-encoding of dynamic_eval.py:92-93, without moving the posteriors or the index vector to the host. */
+/* idx is written for all B*N frames, those at or beyond lengths[b] included; every element of targets and target_lengths is written. */
 int sconf_ctc_collapse(const float* x, int64_t B, int64_t N, int64_t C, const int32_t* lengths, int32_t blank, int32_t* idx,
                        int32_t* targets, int64_t S_cap, int32_t* target_lengths, sconf_stream_t stream);
 

@@ -419,23 +419,27 @@ def sub_conv0_bwd_(dpre0, x, dw, dbias):
     dw += wf.grad.reshape(dw.shape); dbias += bf_.grad
 
 
-def _stage01(x, w0, b0, wd, bd):
+def _stage01(x, w0, b0, wd, bd, round_operands=True, round_act=True):
     # rounding points of the MFMA kernels (subsample_mfma.hip): mel and conv0 taps as bf16 MFMA operands (bias as hi + lo: exact
-    # enough to be f32 here), stage-0 activations stored as bf16, depthwise taps as bf16, f32 accumulation everywhere
+    # enough to be f32 here), stage-0 activations stored as bf16, depthwise taps as bf16, f32 accumulation everywhere.
+    # The VALU kernels (subsample.hip, SCONF_SUB_MFMA=0) keep the mel and all taps in f32 (round_operands=False); their forward
+    # stores the stage-0 activations as bf16 in LDS, their backward recomputes them in f32 (round_act=False).
     Cc = w0.shape[0]
-    y0 = F.conv2d(_q(x.to(f32)).transpose(1, 2).unsqueeze(1), _q(w0).reshape(Cc, 1, 3, 3), b0, stride=2, padding=1)
-    return F.conv2d(_q(F.silu(y0)), _q(wd).reshape(Cc, 1, 3, 3), bd, stride=2, padding=1, groups=Cc).permute(0, 2, 3, 1)
+    qo = _q if round_operands else (lambda t: t)
+    qa = _q if round_act else (lambda t: t)
+    y0 = F.conv2d(qo(x.to(f32)).transpose(1, 2).unsqueeze(1), qo(w0).reshape(Cc, 1, 3, 3), b0, stride=2, padding=1)
+    return F.conv2d(qa(F.silu(y0)), qo(wd).reshape(Cc, 1, 3, 3), bd, stride=2, padding=1, groups=Cc).permute(0, 2, 3, 1)
 
 
-def sub_stage01_fwd(x, w0, b0, wd, bd):
-    return _stage01(x, w0, b0, wd, bd).contiguous().to(torch.bfloat16)
+def sub_stage01_fwd(x, w0, b0, wd, bd, valu=False):
+    return _stage01(x, w0, b0, wd, bd, round_operands=not valu).contiguous().to(torch.bfloat16)
 
 
-def sub_stage01_bwd_(dd1, x, w0, b0, wd, dw0, db0, dwd, dbd):
+def sub_stage01_bwd_(dd1, x, w0, b0, wd, dw0, db0, dwd, dbd, valu=False):
     ps = [t.detach().clone().requires_grad_(True) for t in (w0, b0, wd)]
     bdz = torch.zeros_like(b0).requires_grad_(True)
     with torch.enable_grad():
-        _stage01(x, ps[0], ps[1], ps[2], bdz).backward(dd1.to(f32))
+        _stage01(x, ps[0], ps[1], ps[2], bdz, round_operands=not valu, round_act=not valu).backward(dd1.to(f32))
     dw0 += ps[0].grad.reshape(dw0.shape); db0 += ps[1].grad; dwd += ps[2].grad.reshape(dwd.shape); dbd += bdz.grad
 
 
