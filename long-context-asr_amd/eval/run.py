@@ -1,4 +1,5 @@
-"""Evaluation driver — the per-recording loop of eval/run.py:71-125 of the reference without its dataset loading.
+"""Evaluation driver — the per-recording loop of eval/run.py:71-125 of the reference without its dataset loading; `transcribe` and
+`spectrograms_of` put the audio front end (utils/audio_tools.py) before it, so that a 16 kHz waveform is enough.
 
 Four steps per recording, as there: log-probs in one of three modes, greedy CTC decoding, text normalisation, and
 word_error_rate_detail.  The modes are the reference's `--evaluation_mode` choices (run.py:37-44):
@@ -12,11 +13,13 @@ The reference normalises with Whisper's EnglishTextNormalizer, which is not a de
 to the identity (`.lower()` is applied as in the reference)."""
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Iterable, List, Optional, Tuple
 
 import torch
 
 from ..decoding.greedy import GreedyCTCDecoder
+from ..utils.audio_tools import grab_left_channel, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
 from .utils import fetch_logits as moving_average_eval
 from .wer import word_error_rate_detail
@@ -34,26 +37,37 @@ def _windowed_modules(model) -> List[torch.nn.Module]:
     return [m for m in model.modules() if hasattr(m, 'left_window') and hasattr(m, 'right_window')]
 
 
-def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
-             evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
-             include_per_recording_evaluations: bool = False, args=None) -> List[dict]:
-    """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
-    of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last."""
+@contextlib.contextmanager
+def _evaluation_mode(model, evaluation_mode: str, seq_len: int, args):
+    """(eval_fn, seq_len) of a mode.  'windowed_attention' limits every attention module for the duration of the block and restores
+    the windows afterwards, also when the model raises."""
     if evaluation_mode not in MODES:
         raise ValueError(f'evaluation_mode must be one of {MODES}, got {evaluation_mode!r}')
-    args = _Args() if args is None else args
-    normalize = (lambda s: s) if normalize is None else normalize
     eval_fn = buffered_eval if evaluation_mode == 'buffered' else moving_average_eval
-    decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)
     modules = _windowed_modules(model) if evaluation_mode == 'windowed_attention' else []
     saved = [(m.left_window, m.right_window) for m in modules]
-    all_texts, all_golds, wer_data = [], [], []
     try:
         if evaluation_mode == 'windowed_attention':
             window = seq_len // model.subsampling.subsampling_factor // 2      # // 2: applied in both directions
             for m in modules:
                 m.left_window = m.right_window = window
             seq_len = int(getattr(args, 'max_sequence_length', 3600000))       # 10 hours
+        yield eval_fn, seq_len
+    finally:
+        for m, (lw, rw) in zip(modules, saved):
+            m.left_window, m.right_window = lw, rw
+
+
+def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
+             evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
+             include_per_recording_evaluations: bool = False, args=None) -> List[dict]:
+    """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
+    of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last."""
+    args = _Args() if args is None else args
+    normalize = (lambda s: s) if normalize is None else normalize
+    all_texts, all_golds, wer_data = [], [], []
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)
         for rec_id, spec, gold_text in recordings:
             logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer,
                              use_tqdm=False, return_numpy=False)
@@ -64,9 +78,25 @@ def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeniz
                 wer, words, ins_rate, del_rate, sub_rate = word_error_rate_detail(hypotheses=[out], references=[gold_text])
                 wer_data.append({'recording': rec_id, 'wer': wer, 'words': words, 'ins_rate': ins_rate, 'del_rate': del_rate,
                                  'sub_rate': sub_rate})
-    finally:
-        for m, (lw, rw) in zip(modules, saved):
-            m.left_window, m.right_window = lw, rw
     wer, words, ins_rate, del_rate, sub_rate = word_error_rate_detail(hypotheses=all_texts, references=all_golds)
     wer_data.append({'recording': 'all', 'wer': wer, 'words': words, 'ins_rate': ins_rate, 'del_rate': del_rate, 'sub_rate': sub_rate})
     return wer_data
+
+
+def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
+               normalise: bool = True, args=None) -> str:
+    """Waveform to transcript: 16 kHz waveform (L,) or (channels, L) on the GPU -> spectrogram (utils.audio_tools.to_spectogram of
+    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding.  The text is returned as decoded (evaluate's
+    `normalize` and lower() belong to scoring)."""
+    args = _Args() if args is None else args
+    spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                         return_numpy=False)
+        return GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)(logits)
+
+
+def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True):
+    """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time."""
+    for rec_id, waveform, gold_text in recordings:
+        yield rec_id, to_spectogram(grab_left_channel(waveform), global_normalisation=normalise), gold_text
