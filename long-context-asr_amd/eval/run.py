@@ -14,12 +14,14 @@ to the identity (`.lower()` is applied as in the reference)."""
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import Callable, Iterable, List, Optional, Tuple
 
 import torch
 
+from ..decoding.align import ctc_forced_align, word_timestamps
 from ..decoding.greedy import GreedyCTCDecoder
-from ..utils.audio_tools import grab_left_channel, to_spectogram
+from ..utils.audio_tools import HOP_LENGTH, SR, grab_left_channel, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
 from .utils import fetch_logits as moving_average_eval
 from .wer import word_error_rate_detail
@@ -100,3 +102,27 @@ def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normali
     """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time."""
     for rec_id, waveform, gold_text in recordings:
         yield rec_id, to_spectogram(grab_left_channel(waveform), global_normalisation=normalise), gold_text
+
+
+def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
+          args=None) -> List[dict]:
+    """Word timestamps of a known transcript: log-probs of spec (1, F, T) exactly as `evaluate` computes them in `evaluation_mode`,
+    CTC forced alignment of tokenizer.encode(text) on the GPU, then decoding.align.word_timestamps - a list of
+    {'word', 'startTime', 'endTime', 'logp'} with times in the reference's '12.34s' form (one frame of the log-probs is
+    subsampling_factor * HOP_LENGTH / SR seconds).  Raises ValueError when the transcript has more labels than the frames can emit."""
+    args = _Args() if args is None else args
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                         return_numpy=False)
+    ids = [int(i) for i in tokenizer.encode(text)]
+    al = ctc_forced_align(logits, ids, blank=model.decoder.num_classes - 1)
+    if not math.isfinite(float(al.score)):
+        raise ValueError(f'transcript of {len(ids)} labels cannot be emitted in {logits.shape[0]} frames')
+    return word_timestamps(ids, al.spans, tokenizer, model.subsampling.subsampling_factor * HOP_LENGTH / SR, token_logp=al.token_logp)
+
+
+def align_waveform(model, waveform: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int,
+                   evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None) -> List[dict]:
+    """`align` from a 16 kHz waveform (L,) or (channels, L) on the GPU: the spectrogram of the left channel in front, as `transcribe`."""
+    spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
+    return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args)
