@@ -1,7 +1,7 @@
 """Evaluation driver — the per-recording loop of eval/run.py:71-125 of the reference without its dataset loading; `transcribe` and
 `spectrograms_of` put the audio front end (utils/audio_tools.py) before it, so that a 16 kHz waveform is enough.
 
-Four steps per recording, as there: log-probs in one of three modes, greedy CTC decoding, text normalisation, and
+Four steps per recording, as there: log-probs in one of three modes, CTC decoding (greedy, or beam search for beam_width > 1), text normalisation, and
 word_error_rate_detail.  The modes are the reference's `--evaluation_mode` choices (run.py:37-44):
   'averaged_moving_window'   eval.utils.fetch_logits: overlapping windows, posteriors averaged where they overlap;
   'buffered'                 eval.buffered_transcription.fetch_logits: chunks transcribed inside a context buffer;
@@ -20,6 +20,7 @@ from typing import Callable, Iterable, List, Optional, Tuple
 import torch
 
 from ..decoding.align import ctc_forced_align, word_timestamps
+from ..decoding.beam import BeamSearchCTCDecoder
 from ..decoding.greedy import GreedyCTCDecoder
 from ..utils.audio_tools import HOP_LENGTH, SR, grab_left_channel, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
@@ -27,6 +28,16 @@ from .utils import fetch_logits as moving_average_eval
 from .wer import word_error_rate_detail
 
 MODES = ('averaged_moving_window', 'buffered', 'windowed_attention')
+
+
+def _decoder(model, tokenizer, beam_width: int):
+    """beam_width 1: the greedy decoder (per-frame argmax); above: prefix beam search without a language model."""
+    if beam_width < 1:
+        raise ValueError(f'beam_width must be at least 1, got {beam_width}')
+    blank = model.decoder.num_classes - 1
+    if beam_width == 1:
+        return GreedyCTCDecoder(tokenizer=tokenizer, blank_id=blank)
+    return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width)
 
 
 class _Args:
@@ -62,14 +73,15 @@ def _evaluation_mode(model, evaluation_mode: str, seq_len: int, args):
 
 def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
              evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
-             include_per_recording_evaluations: bool = False, args=None) -> List[dict]:
+             include_per_recording_evaluations: bool = False, args=None, beam_width: int = 1) -> List[dict]:
     """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
-    of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last."""
+    of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last.
+    beam_width > 1 decodes with decoding.beam.BeamSearchCTCDecoder instead of the per-frame argmax."""
     args = _Args() if args is None else args
     normalize = (lambda s: s) if normalize is None else normalize
     all_texts, all_golds, wer_data = [], [], []
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
-        decoder = GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)
+        decoder = _decoder(model, tokenizer, beam_width)
         for rec_id, spec, gold_text in recordings:
             logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer,
                              use_tqdm=False, return_numpy=False)
@@ -86,16 +98,16 @@ def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeniz
 
 
 def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
-               normalise: bool = True, args=None) -> str:
+               normalise: bool = True, args=None, beam_width: int = 1) -> str:
     """Waveform to transcript: 16 kHz waveform (L,) or (channels, L) on the GPU -> spectrogram (utils.audio_tools.to_spectogram of
-    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding.  The text is returned as decoded (evaluate's
-    `normalize` and lower() belong to scoring)."""
+    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search.  The text is
+    returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
     args = _Args() if args is None else args
     spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
                          return_numpy=False)
-        return GreedyCTCDecoder(tokenizer=tokenizer, blank_id=model.decoder.num_classes - 1)(logits)
+        return _decoder(model, tokenizer, beam_width)(logits)
 
 
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True):

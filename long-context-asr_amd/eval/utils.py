@@ -13,6 +13,30 @@ from typing import List, Tuple
 import torch
 
 from .. import functional as Fn          # Fn.ops: the HIP op layer (tests swap it for the CPU kernel references)
+from ..utils.audio_tools import total_seconds
+
+
+def decode_beams_lm(logits_list, decoder, beam_width=100, encoded_lengths=None, ds_factor=4):
+    """Mirror of lcasr/eval/utils.py:14-43: beam-search every (N, C) log-prob array of logits_list with `decoder` (a
+    decoding.beam.BeamSearchCTCDecoder; anything with pyctcdecode's decode_beams works) and return (one dict per recording, the best
+    beam of the last one).  'frames' holds word times in seconds of the spectrogram (frame * ds_factor hops), None if ds_factor is
+    None.  There is no language model: ngram_score is lm_score - logit_score = 0 and score = am_score."""
+    decoded_data = []
+    if encoded_lengths is None:
+        encoded_lengths = [len(logits) for logits in logits_list]
+
+    def proc_text_frame(tx_frame):
+        text, frame = tx_frame
+        return {'word': text, 'start': total_seconds(frame[0] * ds_factor), 'end': total_seconds(frame[1] * ds_factor)}
+
+    for logits, length in zip(logits_list, encoded_lengths):
+        beams = decoder.decode_beams(logits=logits[:length], beam_width=beam_width)
+        decoded_data.append({'text': beams[0].text,
+                             'frames': [proc_text_frame(el) for el in beams[0].text_frames] if ds_factor is not None else None,
+                             'ngram_score': beams[0].lm_score - beams[0].logit_score,
+                             'am_score': beams[0].logit_score,
+                             'score': beams[0].lm_score})
+    return decoded_data, beams[0]
 
 
 def window_plan(spec_n: int, seq_len: int, overlap: int) -> List[Tuple[int, int]]:
