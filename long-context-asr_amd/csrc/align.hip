@@ -42,9 +42,6 @@ inline Geometry geometry(int64_t Smax) {
 inline int label_pitch(int64_t Smax) { return (int)((Smax + 7) / 8 * 8 + 8); }
 // back-pointer row: a multiple of 48 bytes, so that the last busy thread's 12- or 16-byte store ends inside its own row
 inline int bp_pitch(int64_t Smax) { return (int)((2 * Smax + 1 + 47) / 48 * 48); }
-inline int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
-
-__device__ __forceinline__ int len_of(const int* v, int b, int dflt) { return v ? v[b] : dflt; }
 
 // One workgroup per (sample, frame) row: the frame's log-probs go to LDS with 16-byte loads, the S + 1 emissions are gathered from
 // there (ctc_gather_kernel's scheme).  Frames at or past the sample's length are never read by the lattice and are not written.

@@ -39,12 +39,9 @@ constexpr unsigned long long H0 = 0x9E3779B97F4A7C15ull;
 
 inline int pow2ceil(long n) { int p = 2; while (p < n) p <<= 1; return p; }
 inline int search_threads(long W, long K) { return std::min(std::max(pow2ceil(W * (K + 1)) / 2, 64), 1024); }
-inline int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
 inline bool sizes_ok(int64_t W, int64_t K) { return W >= 1 && W <= MAX_W && K >= 1 && K <= MAX_K; }
 
 struct Fin { int node, len; double score; };
-
-__device__ __forceinline__ int len_of(const int* v, int b, int dflt) { return v ? v[b] : dflt; }
 
 __device__ __forceinline__ double lse2(double a, double b) {
     const double m = fmax(a, b);

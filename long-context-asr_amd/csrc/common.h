@@ -39,6 +39,9 @@ int stage01_mfma_slabs(int64_t F, int64_t C, int bwd);
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }   // v_cvt_pk_bf16_f32 (RNE, NaN-safe)
 
+// a sample's length: v[b], or dflt where the caller passed no length vector
+__device__ __forceinline__ int len_of(const int* v, int b, int dflt) { return v ? v[b] : dflt; }
+
 template <typename T> __device__ __forceinline__ float ld_f(const T* p);
 template <> __device__ __forceinline__ float ld_f<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ld_f<bf16>(const bf16* p) { return (float)*p; }
@@ -153,6 +156,7 @@ __device__ __forceinline__ float dgeluf_(float x) {
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+static inline int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }    // workspace sections start on 256-byte boundaries
 static inline int conv_out(long n) { return (int)((n - 1) / 2 + 1); }          // output length of a 3-tap, stride-2, pad-1 convolution
 // CUs of the current device, asked for once; 256 (an MI355X) if the runtime does not say
 static inline int num_cus() {

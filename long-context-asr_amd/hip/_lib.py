@@ -10,8 +10,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), 'lib', 'libsconf_hip.so')
 
 _lib = None
+_units = []       # (prototypes, plain) of every registered ABI unit, the core one (include/sconf.h) first
+_typed = {}       # name -> the ctypes function, once the loaded library's symbol carries its argtypes and restype
 
-vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
+vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
 
 # name -> argtypes (all return int status; 0 = ok).  Must match include/sconf.h.
 PROTOTYPES = {
@@ -94,8 +96,31 @@ PLAIN = {
 }
 
 
+def _type(lib, prototypes, plain):
+    for name, (args, res) in [(n, (a, C.c_int)) for n, a in prototypes.items()] + list(plain.items()):
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, res
+        _typed[name] = fn
+
+
+def register(prototypes, plain):
+    """Add an ABI unit's two tables (hip/audio.py, hip/align.py, hip/beam.py at import; the core tables below).  A name can be
+    registered once; a library that is already loaded gets the new entry points typed at once."""
+    names = list(prototypes) + list(plain)
+    taken = {n for unit in _units for table in unit for n in table}
+    twice = sorted(n for n in names if n in taken or names.count(n) > 1)
+    if twice:
+        raise ValueError(f'entry points registered twice: {", ".join(twice)}')
+    _units.append((prototypes, plain))
+    if _lib is not None:
+        _type(_lib, prototypes, plain)
+
+
+register(PROTOTYPES, PLAIN)
+
+
 def load():
-    """Load the library once; raise loudly if it is not built."""
+    """Load the library once, with every registered entry point typed; raise loudly if it is not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -104,20 +129,22 @@ def load():
             f'libsconf_hip.so not found at {LIB_PATH}. Build it with `python -c "import __graft_entry__ as g; g.build()"` '
             f'or `make -C long-context-asr_amd/csrc`. There is no CPU/PyTorch fallback for the HIP path.')
     lib = C.CDLL(LIB_PATH)
-    for name, args in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    for name, (args, res) in PLAIN.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = res
+    for prototypes, plain in _units:
+        _type(lib, prototypes, plain)
     _lib = lib
     return lib
 
 
+def bound():
+    """name -> (argtypes, restype) as the loaded library's functions carry them (for the tests)."""
+    return {name: (list(fn.argtypes), fn.restype) for name, fn in _typed.items()}
+
+
 def call(name: str, *args):
     lib = load()
-    rc = getattr(lib, name)(*args)
+    fn = _typed.get(name)
+    if fn is None:                     # never call a symbol with ctypes defaults: an int64_t size would go through as a C int
+        raise RuntimeError(f'{name} is not a typed entry point: its unit (lcasr_amd.hip.<unit>) has not registered it')
+    rc = fn(*args)
     if rc != 0:
         raise RuntimeError(f'{name} failed: {lib.sconf_last_error().decode()}')

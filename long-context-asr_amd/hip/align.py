@@ -11,9 +11,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .ops import _p, _stream, _workspace, require_gpu
-
-vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
+from ._lib import vp, i64, i32
+from .ops import _chk_log_probs, _chk_lengths, _p, _stream, _workspace, require_gpu
 
 # name -> argtypes (status-returning launchers).  Must match include/sconf_align.h.
 PROTOTYPES = {
@@ -29,7 +28,8 @@ PLAIN = {
     'sconf_align_workspace': ([i64, i64, i64], C.c_int64),
 }
 
-_bound = None
+_lib.register(PROTOTYPES, PLAIN)
+load = _lib.load
 
 
 class Alignment(NamedTuple):
@@ -39,21 +39,6 @@ class Alignment(NamedTuple):
     spans: torch.Tensor
     token_logp: torch.Tensor
     score: torch.Tensor
-
-
-def load():
-    """The library of _lib.load() with the sconf_align_* entry points typed."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, args in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, C.c_int
-        for name, (args, res) in PLAIN.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, res
-        _bound = lib
-    return lib
 
 
 def max_labels() -> int:
@@ -74,24 +59,12 @@ def align_workspace(B: int, N: int, Smax: int) -> int:
     return n
 
 
-def _lengths(t: Optional[torch.Tensor], B: int, what: str):
-    if t is None:
-        return None
-    require_gpu(t, what)
-    if t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
-        raise TypeError(f'ctc_align: {what} must be a contiguous (B,) int32 tensor')
-    return t
-
-
 def ctc_align(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths: Optional[torch.Tensor],
               target_lengths: Optional[torch.Tensor], blank: int) -> Alignment:
     """log_probs (B, N, C) f32, targets (B, Smax) int32, lengths (B,) int32 or None (= N / Smax) -> Alignment of device tensors.
     See include/sconf_align.h for the semantics."""
-    require_gpu(log_probs, 'log_probs')
+    B, N, Cn = _chk_log_probs(log_probs, 'ctc_align')
     require_gpu(targets, 'targets')
-    if log_probs.dtype != torch.float32 or log_probs.dim() != 3 or not log_probs.is_contiguous():
-        raise TypeError('ctc_align: log_probs must be a contiguous (B, N, C) float32 tensor')
-    B, N, Cn = log_probs.shape
     if targets.dtype != torch.int32 or targets.dim() != 2 or targets.shape[0] != B or not targets.is_contiguous():
         raise TypeError('ctc_align: targets must be a contiguous (B, Smax) int32 tensor')
     Smax = targets.shape[1]
@@ -99,14 +72,14 @@ def ctc_align(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths: Opt
         raise ValueError(f'ctc_align: {Smax} labels: at most {max_labels()} (a lattice of {2 * max_labels() + 1} states) are supported')
     if B < 1 or N < 1:
         raise ValueError(f'ctc_align: empty input B={B} N={N}')
-    input_lengths, target_lengths = _lengths(input_lengths, B, 'input_lengths'), _lengths(target_lengths, B, 'target_lengths')
+    _chk_lengths(input_lengths, B, 'ctc_align', 'input_lengths')
+    _chk_lengths(target_lengths, B, 'ctc_align', 'target_lengths')
     dev = log_probs.device
     out = Alignment(torch.empty(B, N, dtype=torch.int32, device=dev), torch.empty(B, N, dtype=torch.int32, device=dev),
                     torch.empty(B, Smax, 2, dtype=torch.int32, device=dev), torch.empty(B, Smax, dtype=torch.float32, device=dev),
                     torch.empty(B, dtype=torch.float64, device=dev))
     nbytes = align_workspace(B, N, Smax)
     ws = _workspace(nbytes, dev)
-    load()
     _lib.call('sconf_align_ctc', _p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths), _p(out.path), _p(out.labels),
               _p(out.spans), _p(out.token_logp), _p(out.score), _p(ws), nbytes, B, N, Cn, Smax, int(blank), _stream())
     return out

@@ -10,9 +10,8 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._lib import vp, i64, i32
 from .ops import BF16, F32, _p, _stream, _workspace, require_gpu
-
-vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
 
 # name -> argtypes (status-returning launchers).  Must match include/sconf_audio.h.
 PROTOTYPES = {
@@ -27,22 +26,8 @@ PLAIN = {
 N_FFT, HOP, WIN, N_BINS, PAD = 512, 160, 400, 257, 256
 MAX_MELS = 128
 
-_bound = None
-
-
-def load():
-    """The library of _lib.load() with the sconf_audio_* entry points typed."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, args in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, C.c_int
-        for name, (args, res) in PLAIN.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, res
-        _bound = lib
-    return lib
+_lib.register(PROTOTYPES, PLAIN)
+load = _lib.load
 
 
 def tile_frames() -> int:
@@ -91,7 +76,6 @@ def melspec(wave: torch.Tensor, lengths: Optional[torch.Tensor], fb: torch.Tenso
     raw = torch.empty(B, n_mels, T, dtype=torch.float32, device=wave.device) if normalise and out_dtype == torch.bfloat16 else None
     nbytes = melspec_workspace(B, T, n_mels)
     ws = _workspace(nbytes, wave.device)
-    load()
     _lib.call('sconf_audio_melspec', _p(wave), wave.stride(0) if B > 1 else L, _p(lengths), L, _p(fb), _p(ranges), _p(spec),
               F32 if out_dtype == torch.float32 else BF16, _p(raw), int(bool(normalise)), _p(ws), nbytes, B, T, n_mels, _stream())
     return spec

@@ -11,9 +11,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
-from .ops import _p, _stream, _workspace, require_gpu
-
-vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
+from ._lib import vp, i64, i32, f32, f64
+from .ops import _chk_log_probs, _chk_lengths, _p, _stream, _workspace
 
 # name -> argtypes (status-returning launchers).  Must match include/sconf_beam.h.
 PROTOTYPES = {
@@ -30,7 +29,8 @@ PLAIN = {
     'sconf_beam_workspace': ([i64, i64, i64, i64], C.c_int64),
 }
 
-_bound = None
+_lib.register(PROTOTYPES, PLAIN)
+load = _lib.load
 
 
 class Beams(NamedTuple):
@@ -41,21 +41,6 @@ class Beams(NamedTuple):
     lengths: torch.Tensor
     token_frames: torch.Tensor
     scores: torch.Tensor
-
-
-def load():
-    """The library of _lib.load() with the sconf_beam_* entry points typed."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, args in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, C.c_int
-        for name, (args, res) in PLAIN.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, res
-        _bound = lib
-    return lib
 
 
 def max_width() -> int:
@@ -78,16 +63,10 @@ def ctc_beam(log_probs: torch.Tensor, input_lengths: Optional[torch.Tensor], bla
              token_min_logp: float, beam_prune_logp: float, max_tokens_per_frame: int, max_len: int) -> Beams:
     """log_probs (B, N, C) f32, input_lengths (B,) int32 or None (= N) -> Beams of device tensors.  See include/sconf_beam.h for
     the semantics."""
-    require_gpu(log_probs, 'log_probs')
-    if log_probs.dtype != torch.float32 or log_probs.dim() != 3 or not log_probs.is_contiguous():
-        raise TypeError('ctc_beam: log_probs must be a contiguous (B, N, C) float32 tensor')
-    B, N, Cn = log_probs.shape
+    B, N, Cn = _chk_log_probs(log_probs, 'ctc_beam')
     if B < 1 or N < 1:
         raise ValueError(f'ctc_beam: empty input B={B} N={N}')
-    if input_lengths is not None:
-        require_gpu(input_lengths, 'input_lengths')
-        if input_lengths.dtype != torch.int32 or tuple(input_lengths.shape) != (B,) or not input_lengths.is_contiguous():
-            raise TypeError('ctc_beam: input_lengths must be a contiguous (B,) int32 tensor')
+    _chk_lengths(input_lengths, B, 'ctc_beam', 'input_lengths')
     W, nb, K, L = int(beam_width), int(nbest), int(max_tokens_per_frame), int(max_len)
     if not 1 <= nb <= W or L < 1:
         raise ValueError(f'ctc_beam: nbest={nb} must be in 1..beam_width={W} and max_len={L} at least 1')
@@ -97,7 +76,6 @@ def ctc_beam(log_probs: torch.Tensor, input_lengths: Optional[torch.Tensor], bla
                 torch.empty(B, nb, dtype=torch.int32, device=dev), torch.empty(B, nb, L, dtype=torch.int32, device=dev),
                 torch.empty(B, nb, dtype=torch.float64, device=dev))
     ws = _workspace(nbytes, dev)
-    load()
     _lib.call('sconf_beam_ctc', _p(log_probs), _p(input_lengths), _p(out.count), _p(out.tokens), _p(out.lengths), _p(out.token_frames),
               _p(out.scores), _p(ws), nbytes, B, N, Cn, int(blank), W, nb, float(token_min_logp), float(beam_prune_logp), K, L, _stream())
     return out

@@ -60,6 +60,23 @@ def _chk(t: torch.Tensor, name: str, dtype=None):
     return t
 
 
+def _chk_log_probs(t: torch.Tensor, op: str):
+    """The decoding units' main input: a contiguous (B, N, C) float32 GPU tensor.  Returns its shape."""
+    require_gpu(t, 'log_probs')
+    if t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+        raise TypeError(f'{op}: log_probs must be a contiguous (B, N, C) float32 tensor')
+    return t.shape
+
+
+def _chk_lengths(t: Optional[torch.Tensor], B: int, op: str, name: str):
+    """Their optional per-sample lengths: None, or a contiguous (B,) int32 GPU tensor."""
+    if t is not None:
+        require_gpu(t, name)
+        if t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise TypeError(f'{op}: {name} must be a contiguous (B,) int32 tensor')
+    return t
+
+
 # ------------------------------------------------------------------------------------------------
 # GEMM
 # ------------------------------------------------------------------------------------------------

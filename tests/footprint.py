@@ -1,7 +1,7 @@
 """Write-footprint harness: where does an entry point of include/sconf.h write, does it write everything it claims to, and does it
 read any of its outputs or scratch before writing them?  TEST INFRASTRUCTURE, plain importable module (no fixtures, no pytest hooks),
-device-agnostic: tests/test_footprint.py drives it with CPU tensors and small Python "kernels", tests/test_footprint_gpu.py with the
-library's entry points (raw pointers through lcasr_amd.hip._lib.call, as ops._p passes them).
+device-agnostic: tests/test_footprint.py drives it with CPU tensors and small Python "kernels", the GPU tests of every ABI unit with
+the library's entry points (run_on_device: raw pointers through lcasr_amd.hip._lib.call, as ops._p passes them).
 
 Every buffer of one call - inputs, outputs, workspaces, length vectors - is carved out of ONE uint8 arena at 16-byte granularity (the
 flat gradient buffer guarantees no more, so offsets are deliberately NOT rounded to 256 or 512) with a guard band of at least GUARD
@@ -24,6 +24,7 @@ as bf16 / f32 / f64, -1 as an integer), run B with seeded pseudo-random bytes.  
 import ctypes
 import math
 
+import pytest
 import torch
 
 from kernel_test_utils import TOL_BF16, TOL_F32
@@ -271,6 +272,19 @@ def report_line(case, figures):
             f'guard={figures["guard_bytes"]} B checked, max err {" ".join(figures["valued"]) or "-"}')
 
 
+def run_on_device(case, prototypes):
+    """One case of a GPU test: run_case on 'cuda' through lib_launch, every call a launcher of `prototypes`, the report line printed.
+    A launch refused on the host is a failure of this case; a device fault ends the session: nothing more runs on a faulted GPU."""
+    assert {case.name} | {name for name, _ in case.before} <= set(prototypes)
+    try:
+        figures = run_case(case, 'cuda')
+    except RuntimeError as e:
+        if 'HIP error' in str(e) or 'illegal memory access' in str(e):
+            pytest.exit(f'{case.id}: device fault, no further case is launched: {e}', returncode=3)
+        raise
+    print(report_line(case, figures))
+
+
 # ------------------------------------------------------------------------------------------------ layout checks that need no device
 def check_layout(case, prototypes):
     """CPU check of one case: regions disjoint, aligned and guarded; the argument list as long as the prototype (less the stream);
@@ -282,7 +296,7 @@ def check_layout(case, prototypes):
         for i, (a, t) in enumerate(zip(args, prototypes[name])):
             if isinstance(a, Region): assert A.regions.get(a.name) is a, f'{case.id}: {a} is not a region of this arena'
             kind = 'pointer' if isinstance(a, (Region, ctypes.Array, type(None))) else 'float' if isinstance(a, float) else 'int'
-            want = {ctypes.c_void_p: 'pointer', ctypes.c_float: 'float'}.get(t, 'int')
+            want = {ctypes.c_void_p: 'pointer', ctypes.c_float: 'float', ctypes.c_double: 'float'}.get(t, 'int')
             assert isinstance(a, (Region, ctypes.Array, type(None), float, int)) and kind == want, \
                 f'{case.id}: {name} argument {i} is a {want} in the prototype, the case passes {a!r}'
     used = {a.name for _, args in list(case.before) + [(case.name, case.args)] for a in args if isinstance(a, Region)}

@@ -1,10 +1,9 @@
 """CPU tests of CTC forced alignment: the numpy restatement (tests/align_refs.py) against the brute-force definition and against
-hand-written tie cases, the C ABI of the alignment unit (include/sconf_align.h <-> hip/align.py <-> the built library) with its
-host-side queries and refusals, word_timestamps, and eval.run.align on the tiny fixture model with the binding replaced by the
+hand-written tie cases, the host-side queries and refusals of the alignment unit (test_cabi.py holds its binding to
+include/sconf_align.h), word_timestamps, and eval.run.align on the tiny fixture model with the binding replaced by the
 restatement.  The HIP kernels themselves are tested in test_align_gpu.py."""
 import ctypes
 import itertools
-import os
 import re
 
 import numpy as np
@@ -14,7 +13,7 @@ import torch
 import align_refs as AR
 import eval_refs as E
 from common_model import build_from_fixture
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 
 @pytest.fixture
@@ -104,65 +103,13 @@ def test_batched_restatement_marks_padding_infeasible_and_poisoned_samples():
     assert all(torch.equal(a[0], b[0]) for a, b in zip(alone, out))
 
 
-# ---- 3. C ABI of the alignment unit (mirror of test_audio_front_end.py) ------------------------------------------------------
-_CTYPE = {'sconf_stream_t': ctypes.c_void_p, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'float': ctypes.c_float}
-_RESTYPE = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64}
-
-
-def _header_abi():
-    """name -> (argtypes, restype) of include/sconf_align.h; every statement between the extern "C" braces must be a declaration of
-    a sconf_align_* function over the types above: anything else raises."""
-    src = open(os.path.join(ROOT, 'include', 'sconf_align.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    body = re.search(r'extern "C" \{\s*#endif(.*)#ifdef __cplusplus\s*\}', src, flags=re.S).group(1)
-    funcs = {}
-    for stmt in (' '.join(s.split()) for s in body.split(';')):
-        if not stmt:
-            continue
-        m = re.fullmatch(r'(int64_t|int) (sconf_align_[a-z0-9_]+) ?\((.*)\)', stmt)
-        assert m, f'include/sconf_align.h: cannot classify the statement {stmt!r}'
-        ret, name, params = m.groups()
-        args = []
-        for p in ([] if params.strip() == 'void' else params.split(',')):
-            pm = re.fullmatch(r'(?:const )?([a-z0-9_]+) ?(\*?) ?[A-Za-z_][A-Za-z0-9_]*', p.strip())
-            assert pm and (pm.group(2) or pm.group(1) in _CTYPE), f'include/sconf_align.h: {name}: cannot classify the parameter {p!r}'
-            args.append(ctypes.c_void_p if pm.group(2) else _CTYPE[pm.group(1)])
-        assert name not in funcs, f'{name} declared twice'
-        funcs[name] = (args, _RESTYPE[ret])
-    return funcs
-
-
+# ---- 3. host side of the alignment unit (its header is held to the binding in test_cabi.py) --------------------------------
 @pytest.fixture(scope='module')
 def lib():
     import __graft_entry__ as g
     g.build()
     from lcasr_amd.hip import align
     return align.load()
-
-
-def test_align_header_binding_and_exports_agree(lib):
-    from lcasr_amd.hip import _lib, align
-    funcs = _header_abi()
-    assert len(funcs) >= 4 and all(n.startswith('sconf_align_') for n in funcs)
-    assert {'sconf_align_max_labels', 'sconf_align_state_bytes', 'sconf_align_workspace', 'sconf_align_ctc'} <= set(funcs)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for n in funcs:
-        assert hasattr(raw, n), f'{n} declared in include/sconf_align.h but not exported'
-    bound = {n: (a, ctypes.c_int) for n, a in align.PROTOTYPES.items()}
-    assert not set(bound) & set(align.PLAIN)
-    bound.update(align.PLAIN)
-    assert set(bound) == set(funcs), set(bound) ^ set(funcs)
-    for name, (args, res) in funcs.items():
-        got_args, got_res = bound[name]
-        assert got_res is res, f'{name}: returns {res.__name__} in the header, {got_res.__name__} in hip/align.py'
-        assert len(got_args) == len(args), f'{name}: {len(args)} arguments in the header, {len(got_args)} in hip/align.py'
-        for i, (gt, w) in enumerate(zip(got_args, args)):
-            assert gt is w, f'{name}: argument {i} is {w.__name__} in the header, {gt.__name__} in hip/align.py'
-    # the new unit adds nothing to the first one
-    assert not any(n.startswith('sconf_align_') for n in list(_lib.PROTOTYPES) + list(_lib.PLAIN))
-    assert 'sconf_align_' not in open(os.path.join(ROOT, 'include', 'sconf.h')).read()
-    assert 'sconf_align_' not in open(os.path.join(ROOT, 'long-context-asr_amd', 'hip', '_lib.py')).read()
-    assert _lib.load().sconf_version() == 220
 
 
 def test_align_queries(lib):

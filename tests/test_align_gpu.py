@@ -6,8 +6,6 @@ T eps(state type) |score| (the restatement makes the same additions, so the diff
 Launch geometry (sconf_align_threads x sconf_align_states_per_thread, asserted in test_lattice_geometry): 256 x 1 up to 127 labels,
 512 x 1 up to 255, 1024 x 1 / 2 / 4 / 8 / 12 / 16 up to 511 / 1023 / 2047 / 4095 / 6143 / 8191; f32 state from 5113 labels on.  The
 walk back fetches sconf_align_walk_window() = 16 frames at a time."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -172,29 +170,9 @@ def test_refusals_on_the_device_path(K):
 
 
 # ---- 9. footprint -------------------------------------------------------------------------------------------------------------
-def test_every_align_entry_point_has_a_case(K):
-    assert {entry for entry, _ in AC.CASES.values()} | AC.NO_LAUNCH == set(K.PROTOTYPES) | set(K.PLAIN)
-    assert not {entry for entry, _ in AC.CASES.values()} & AC.NO_LAUNCH
-
-
 @pytest.mark.parametrize('id', list(AC.CASES))
 def test_align_footprint(K, id):
-    from lcasr_amd.hip import _lib
-
-    def launch(name, args, buf, views):
-        assert name in K.PROTOTYPES
-        K.load()
-        _lib.call(name, *FP.resolve(args, buf), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        torch.cuda.synchronize()
-
-    case = AC.build(id, K.load())
-    try:
-        figures = FP.run_case(case, 'cuda', launch=launch)
-    except RuntimeError as e:                        # a device fault ends the session: nothing more runs on a faulted GPU
-        if 'HIP error' in str(e) or 'illegal memory access' in str(e):
-            pytest.exit(f'{id}: device fault, no further case is launched: {e}', returncode=3)
-        raise
-    print(FP.report_line(case, figures))
+    FP.run_on_device(AC.build(id, K.load()), K.PROTOTYPES)
 
 
 # ---- 10. model level ------------------------------------------------------------------------------------------------------------

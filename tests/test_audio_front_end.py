@@ -1,10 +1,8 @@
 """CPU tests of the audio front end: the restatement (tests/audio_refs.py) against an independent direct DFT, the filterbank's
 sparsity, the host logic of lcasr_amd.utils.audio_tools and of eval.run.transcribe / spectrograms_of with the binding replaced by
-the restatement, and the C ABI of the audio unit (include/sconf_audio.h <-> hip/audio.py <-> the built library), mirroring
-test_cabi.py.  The HIP kernels themselves are tested in test_audio_front_end_gpu.py."""
+the restatement, and the host-side queries and refusals of the audio unit (test_cabi.py holds its binding to include/sconf_audio.h).
+The HIP kernels themselves are tested in test_audio_front_end_gpu.py."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -12,7 +10,7 @@ import torch
 import audio_refs as AR
 import eval_refs as E
 from common_model import build_from_fixture
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 
 @pytest.fixture
@@ -180,58 +178,7 @@ def test_transcribe_and_spectrograms_of_on_the_tiny_model(emulated_ops, emulated
         R.transcribe(m, wave, tok, 128, 32, evaluation_mode='beam')
 
 
-# ---- C ABI of the audio unit (mirror of test_cabi.py) ------------------------------------------------------------------------
-_CTYPE = {'sconf_stream_t': ctypes.c_void_p, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'float': ctypes.c_float}
-_RESTYPE = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64}
-
-
-def _header_abi():
-    """name -> (argtypes, restype) of include/sconf_audio.h; every statement between the extern "C" braces must be a declaration of
-    a sconf_audio_* function over the types above: anything else raises."""
-    src = open(os.path.join(ROOT, 'include', 'sconf_audio.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    body = re.search(r'extern "C" \{\s*#endif(.*)#ifdef __cplusplus\s*\}', src, flags=re.S).group(1)
-    funcs = {}
-    for stmt in (' '.join(s.split()) for s in body.split(';')):
-        if not stmt:
-            continue
-        m = re.fullmatch(r'(int64_t|int) (sconf_audio_[a-z0-9_]+) ?\((.*)\)', stmt)
-        assert m, f'include/sconf_audio.h: cannot classify the statement {stmt!r}'
-        ret, name, params = m.groups()
-        args = []
-        for p in ([] if params.strip() == 'void' else params.split(',')):
-            pm = re.fullmatch(r'(?:const )?([a-z0-9_]+) ?(\*?) ?[A-Za-z_][A-Za-z0-9_]*', p.strip())
-            assert pm and (pm.group(2) or pm.group(1) in _CTYPE), f'include/sconf_audio.h: {name}: cannot classify the parameter {p!r}'
-            args.append(ctypes.c_void_p if pm.group(2) else _CTYPE[pm.group(1)])
-        assert name not in funcs, f'{name} declared twice'
-        funcs[name] = (args, _RESTYPE[ret])
-    return funcs
-
-
-def test_audio_header_binding_and_exports_agree():
-    import __graft_entry__ as g
-    g.build()
-    from lcasr_amd.hip import _lib, audio
-    funcs = _header_abi()
-    assert len(funcs) >= 3 and all(n.startswith('sconf_audio_') for n in funcs)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for n in funcs:
-        assert hasattr(raw, n), f'{n} declared in include/sconf_audio.h but not exported'
-    bound = {n: (a, ctypes.c_int) for n, a in audio.PROTOTYPES.items()}
-    assert not set(bound) & set(audio.PLAIN)
-    bound.update(audio.PLAIN)
-    assert set(bound) == set(funcs), set(bound) ^ set(funcs)
-    for name, (args, res) in funcs.items():
-        got_args, got_res = bound[name]
-        assert got_res is res, f'{name}: returns {res.__name__} in the header, {got_res.__name__} in hip/audio.py'
-        assert len(got_args) == len(args), f'{name}: {len(args)} arguments in the header, {len(got_args)} in hip/audio.py'
-        for i, (gt, w) in enumerate(zip(got_args, args)):
-            assert gt is w, f'{name}: argument {i} is {w.__name__} in the header, {gt.__name__} in hip/audio.py'
-    # the new unit adds nothing to the first one
-    assert not any(n.startswith('sconf_audio_') for n in list(_lib.PROTOTYPES) + list(_lib.PLAIN))
-    assert 'sconf_audio_' not in open(os.path.join(ROOT, 'include', 'sconf.h')).read()
-
-
+# ---- host side of the audio unit (its header is held to the binding in test_cabi.py) ----------------------------------------
 def test_audio_host_side_validation_and_queries():
     from lcasr_amd.hip import audio
     lib = audio.load()

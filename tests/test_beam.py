@@ -1,11 +1,8 @@
 """CPU tests of CTC prefix beam search: the numpy restatement (tests/beam_refs.py) against the enumeration of every frame path and
-against hand cases, the C ABI of the beam unit (include/sconf_beam.h <-> hip/beam.py <-> the built library) with its host-side
-queries and refusals, and BeamSearchCTCDecoder / decode_beams_lm / evaluate(beam_width=...) on the tiny fixture model with the
+against hand cases, the host-side queries and refusals of the beam unit (test_cabi.py holds its binding to include/sconf_beam.h), and BeamSearchCTCDecoder / decode_beams_lm / evaluate(beam_width=...) on the tiny fixture model with the
 binding replaced by the restatement.  The HIP kernels themselves are tested in test_beam_gpu.py."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +11,7 @@ import torch
 import beam_refs as BR
 import eval_refs as E
 from common_model import build_from_fixture
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 INF = math.inf
 
@@ -141,65 +138,13 @@ def test_the_recreation_case_exists_among_the_first_40_seeds():
         assert st['recreated'] >= 1
 
 
-# ---- 3. C ABI of the beam unit (mirror of test_align.py) ----------------------------------------------------------------------
-_CTYPE = {'sconf_stream_t': ctypes.c_void_p, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'float': ctypes.c_float,
-          'double': ctypes.c_double}
-_RESTYPE = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64}
-
-
-def _header_abi():
-    """name -> (argtypes, restype) of include/sconf_beam.h; every statement between the extern "C" braces must be a declaration of
-    a sconf_beam_* function over the types above: anything else raises."""
-    src = open(os.path.join(ROOT, 'include', 'sconf_beam.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    body = re.search(r'extern "C" \{\s*#endif(.*)#ifdef __cplusplus\s*\}', src, flags=re.S).group(1)
-    funcs = {}
-    for stmt in (' '.join(s.split()) for s in body.split(';')):
-        if not stmt:
-            continue
-        m = re.fullmatch(r'(int64_t|int) (sconf_beam_[a-z0-9_]+) ?\((.*)\)', stmt)
-        assert m, f'include/sconf_beam.h: cannot classify the statement {stmt!r}'
-        ret, name, params = m.groups()
-        args = []
-        for p in ([] if params.strip() == 'void' else params.split(',')):
-            pm = re.fullmatch(r'(?:const )?([a-z0-9_]+) ?(\*?) ?[A-Za-z_][A-Za-z0-9_]*', p.strip())
-            assert pm and (pm.group(2) or pm.group(1) in _CTYPE), f'include/sconf_beam.h: {name}: cannot classify the parameter {p!r}'
-            args.append(ctypes.c_void_p if pm.group(2) else _CTYPE[pm.group(1)])
-        assert name not in funcs, f'{name} declared twice'
-        funcs[name] = (args, _RESTYPE[ret])
-    return funcs
-
-
+# ---- 3. host side of the beam unit (its header is held to the binding in test_cabi.py) ---------------------------------------
 @pytest.fixture(scope='module')
 def lib():
     import __graft_entry__ as g
     g.build()
     from lcasr_amd.hip import beam
     return beam.load()
-
-
-def test_beam_header_binding_and_exports_agree(lib):
-    from lcasr_amd.hip import _lib, beam
-    funcs = _header_abi()
-    assert {'sconf_beam_max_width', 'sconf_beam_max_tokens', 'sconf_beam_workspace', 'sconf_beam_ctc'} <= set(funcs)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for n in funcs:
-        assert hasattr(raw, n), f'{n} declared in include/sconf_beam.h but not exported'
-    bound = {n: (a, ctypes.c_int) for n, a in beam.PROTOTYPES.items()}
-    assert not set(bound) & set(beam.PLAIN)
-    bound.update(beam.PLAIN)
-    assert set(bound) == set(funcs), set(bound) ^ set(funcs)
-    for name, (args, res) in funcs.items():
-        got_args, got_res = bound[name]
-        assert got_res is res, f'{name}: returns {res.__name__} in the header, {got_res.__name__} in hip/beam.py'
-        assert len(got_args) == len(args), f'{name}: {len(args)} arguments in the header, {len(got_args)} in hip/beam.py'
-        for i, (gt, w) in enumerate(zip(got_args, args)):
-            assert gt is w, f'{name}: argument {i} is {w.__name__} in the header, {gt.__name__} in hip/beam.py'
-    # the new unit adds nothing to the first one
-    assert not any(n.startswith('sconf_beam_') for n in list(_lib.PROTOTYPES) + list(_lib.PLAIN))
-    assert 'sconf_beam_' not in open(os.path.join(ROOT, 'include', 'sconf.h')).read()
-    assert 'sconf_beam_' not in open(os.path.join(ROOT, 'long-context-asr_amd', 'hip', '_lib.py')).read()
-    assert _lib.load().sconf_version() == 220
 
 
 def test_beam_queries(lib):

@@ -30,9 +30,7 @@ def test_beam_case_layout(lib, id):
     from lcasr_amd.hip import beam
     c = BC.build(id, lib)
     assert c.name == BC.CASES[id][0]
-    # (the harness knows one floating argument type: a double argument is a Python float in the case, like a float one)
-    protos = {n: [ctypes.c_float if t is ctypes.c_double else t for t in a] for n, a in beam.PROTOTYPES.items()}
-    FP.check_layout(c, protos)
+    FP.check_layout(c, beam.PROTOTYPES)             # (a double argument is a Python float in the case, like a float one)
     assert beam.PROTOTYPES['sconf_beam_ctc'][15] is ctypes.c_float and beam.PROTOTYPES['sconf_beam_ctc'][16] is ctypes.c_double
     assert isinstance(c.args[15], float) and isinstance(c.args[16], float)
     B, N, C, blank, W, nbest = c.args[9:15]

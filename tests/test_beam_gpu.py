@@ -6,7 +6,6 @@ device total within eps of the restatement's can take another decision - and, fr
 queries, that the input reaches what the case is named after.  C = 32 with the blank last unless a case says otherwise.
 
 prepare(name) is the CPU half of a case (input, restatement, conditions) and needs no device."""
-import ctypes
 import math
 
 import pytest
@@ -363,29 +362,9 @@ def test_refusals_on_the_device_path(K):
 
 
 # ---- footprint ------------------------------------------------------------------------------------------------------------------
-def test_every_beam_entry_point_has_a_case(K):
-    assert {entry for entry, _ in BC.CASES.values()} | BC.NO_LAUNCH == set(K.PROTOTYPES) | set(K.PLAIN)
-    assert not {entry for entry, _ in BC.CASES.values()} & BC.NO_LAUNCH
-
-
 @pytest.mark.parametrize('id', list(BC.CASES))
 def test_beam_footprint(K, id):
-    from lcasr_amd.hip import _lib
-
-    def launch(name, args, buf, views):
-        assert name in K.PROTOTYPES
-        K.load()
-        _lib.call(name, *FP.resolve(args, buf), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        torch.cuda.synchronize()
-
-    case = BC.build(id, K.load())
-    try:
-        figures = FP.run_case(case, 'cuda', launch=launch)
-    except RuntimeError as e:                        # a device fault ends the session: nothing more runs on a faulted GPU
-        if 'HIP error' in str(e) or 'illegal memory access' in str(e):
-            pytest.exit(f'{id}: device fault, no further case is launched: {e}', returncode=3)
-        raise
-    print(FP.report_line(case, figures))
+    FP.run_on_device(BC.build(id, K.load()), K.PROTOTYPES)
 
 
 # ---- model level ----------------------------------------------------------------------------------------------------------------

@@ -1,14 +1,29 @@
-"""CPU test: libsconf_hip.so builds (hipcc cross-compiles gfx950 without a GPU), loads, and exports exactly the
-entry points include/sconf.h declares, each bound in hip/_lib.py with the header's signature.  No compute call is made."""
+"""CPU test: libsconf_hip.so builds (hipcc cross-compiles gfx950 without a GPU), loads, and exports exactly the entry points the
+headers under include/ declare, each unit's bound in its own module under hip/ with the header's signature and typed by the one
+loader of hip/_lib.py.  No compute call is made."""
 import ctypes
+import importlib
 import os
 import re
+import subprocess
+import sys
 
+import pytest
+
+from cabi_header import assert_binding_is_header, header_abi
 from conftest import ROOT
 
+# unit -> (header, binding module under hip/, name prefix, least number of declared names, names that must be among them)
+UNITS = {
+    'core': ('sconf.h', '_lib', 'sconf_', 27, set()),
+    'audio': ('sconf_audio.h', 'audio', 'sconf_audio_', 3, set()),
+    'align': ('sconf_align.h', 'align', 'sconf_align_', 4, {'sconf_align_max_labels', 'sconf_align_state_bytes', 'sconf_align_workspace', 'sconf_align_ctc'}),
+    'beam': ('sconf_beam.h', 'beam', 'sconf_beam_', 4, {'sconf_beam_max_width', 'sconf_beam_max_tokens', 'sconf_beam_workspace', 'sconf_beam_ctc'}),
+}
 
-def _declared():
-    src = open(os.path.join(ROOT, 'include', 'sconf.h')).read()
+
+def _declared(header):
+    src = open(os.path.join(ROOT, 'include', header)).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
     return sorted(set(re.findall(r'\b(sconf_[a-z0-9_]+)\s*\(', src)))
 
@@ -19,75 +34,86 @@ def test_library_exports_every_declared_symbol():
     from lcasr_amd.hip import _lib
     assert os.path.exists(_lib.LIB_PATH)
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    names = _declared()
-    assert len(names) >= 27
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in include/sconf.h but not exported'
-    bound = set(_lib.PROTOTYPES) | set(_lib.PLAIN)
-    assert bound == set(names), (bound ^ set(names))
+    for header in (u[0] for u in UNITS.values()):
+        for n in _declared(header):
+            assert hasattr(lib, n), f'{n} declared in include/{header} but not exported'
     lib.sconf_version.restype = ctypes.c_int
-    assert lib.sconf_version() >= 100
+    assert lib.sconf_version() == 220
     lib.sconf_last_error.restype = ctypes.c_char_p
     assert isinstance(lib.sconf_last_error(), bytes)
 
 
-_CTYPE = {'sconf_stream_t': ctypes.c_void_p, 'int64_t': ctypes.c_int64, 'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'float': ctypes.c_float}
-_RESTYPE = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'const char*': ctypes.c_char_p}
-
-
-def _header_abi():
-    """(name -> (argtypes, restype), enumerator -> value) of include/sconf.h.  Every statement between the extern "C" braces must be
-    the stream typedef, an anonymous enum or a function declaration over the types above: anything else raises."""
-    src = open(os.path.join(ROOT, 'include', 'sconf.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    body = re.search(r'extern "C" \{\s*#endif(.*)#ifdef __cplusplus\s*\}', src, flags=re.S).group(1)
-    funcs, enums = {}, {}
-    for stmt in (' '.join(s.split()) for s in body.split(';')):
-        if not stmt or stmt == 'typedef struct ihipStream_t* sconf_stream_t':
-            continue
-        m = re.fullmatch(r'enum \{(.*)\}', stmt)
-        if m:
-            for item in m.group(1).split(','):
-                k, v = re.fullmatch(r'\s*(SCONF_[A-Z0-9_]+) = (\d+)\s*', item).groups()
-                assert k not in enums, k
-                enums[k] = int(v)
-            continue
-        m = re.fullmatch(r'(const char\*|int64_t|int) (sconf_[a-z0-9_]+) ?\((.*)\)', stmt)
-        assert m, f'include/sconf.h: cannot classify the statement {stmt!r}'
-        ret, name, params = m.groups()
-        args = []
-        for p in ([] if params.strip() == 'void' else params.split(',')):
-            p = p.strip()
-            pm = re.fullmatch(r'(?:const )?([a-z0-9_]+) ?(\*?) ?[A-Za-z_][A-Za-z0-9_]*', p)
-            assert pm and (pm.group(2) or pm.group(1) in _CTYPE), f'include/sconf.h: {name}: cannot classify the parameter {p!r}'
-            args.append(ctypes.c_void_p if pm.group(2) else _CTYPE[pm.group(1)])
-        assert name not in funcs, f'{name} declared twice'
-        funcs[name] = (args, _RESTYPE[ret])
-    return funcs, enums
-
-
-def test_bindings_and_enums_match_the_header_signature_for_signature():
-    """hip/_lib.py types every call by hand: each argument list and return type must be the header's, and the op layer's enum
-    values the header's enumerators.  (A swapped int / int64_t or a dropped argument would be a miscall into a kernel.)"""
+@pytest.mark.parametrize('unit', list(UNITS))
+def test_bindings_and_enums_match_the_header_signature_for_signature(unit):
+    """Every unit types its calls by hand: each argument list and return type must be the header's (every declared name is exported:
+    the test above), and the op layer's enum values the header's enumerators.  The units add nothing to the first one: sconf.h, the
+    core tables and the text of _lib.py name none of their entry points."""
     from lcasr_amd.hip import _lib, ops
-    funcs, enums = _header_abi()
-    assert sorted(funcs) == _declared()
-    bound = {n: (a, ctypes.c_int) for n, a in _lib.PROTOTYPES.items()}
-    assert not set(bound) & set(_lib.PLAIN)
-    bound.update(_lib.PLAIN)
-    assert set(bound) == set(funcs)
-    for name, (args, res) in funcs.items():
-        got_args, got_res = bound[name]
-        assert got_res is res, f'{name}: returns {res.__name__} in the header, {got_res.__name__} in _lib.py'
-        assert len(got_args) == len(args), f'{name}: {len(args)} arguments in the header, {len(got_args)} in _lib.py'
-        for i, (g, w) in enumerate(zip(got_args, args)):
-            assert g is w, f'{name}: argument {i} is {w.__name__} in the header, {g.__name__} in _lib.py'
+    header, module, prefix, at_least, required = UNITS[unit]
+    binding = importlib.import_module('lcasr_amd.hip.' + module)
+    funcs, enums = header_abi(header, prefix)
+    assert sorted(funcs) == _declared(header) and len(funcs) >= at_least and required <= set(funcs)
+    assert_binding_is_header(funcs, binding.PROTOTYPES, binding.PLAIN, f'hip/{module}.py')
+    if unit != 'core':
+        assert not enums
+        assert not any(n.startswith(prefix) for n in list(_lib.PROTOTYPES) + list(_lib.PLAIN))
+        assert prefix not in open(os.path.join(ROOT, 'include', 'sconf.h')).read()
+        assert prefix not in open(os.path.join(ROOT, 'long-context-asr_amd', 'hip', '_lib.py')).read()
+        return
     assert (ops.F32, ops.BF16) == (enums['SCONF_F32'], enums['SCONF_BF16'])
     assert ops.ACT and all(v == enums['SCONF_ACT_' + k.upper()] for k, v in ops.ACT.items())
     assert ops.LAYOUT == {k[len('SCONF_GEMM_'):].lower(): v for k, v in enums.items() if k.startswith('SCONF_GEMM_')}
     names = {'layer_norm': 'SCONF_NORM_LAYER', 'rms_norm': 'SCONF_NORM_RMS', 'rms_norm_apex': 'SCONF_NORM_RMS_APEX'}
     assert ops.NORM_MODE == {k: enums[n] for k, n in names.items()}
     assert len(names) == sum(k.startswith('SCONF_NORM_') for k in enums)
+
+
+_ORDER_CHILD = '''
+import ctypes, sys
+from lcasr_amd.hip import _lib
+if sys.argv[1] == 'load-first': _lib.load()
+from lcasr_amd.hip import align, audio, beam
+lib = _lib.load()
+for unit in (audio, align, beam):
+    for name, args in unit.PROTOTYPES.items():
+        assert list(getattr(lib, name).argtypes) == args and getattr(lib, name).restype is ctypes.c_int, name
+        assert _lib.bound()[name] == (args, ctypes.c_int), name
+    for name, (args, res) in unit.PLAIN.items():
+        assert list(getattr(lib, name).argtypes) == args and getattr(lib, name).restype is res, name
+assert list(lib.sconf_beam_ctc.argtypes) == beam.PROTOTYPES['sconf_beam_ctc'] and lib.sconf_beam_workspace.restype is ctypes.c_int64
+assert set(_lib.bound()) == {n for u in (_lib, audio, align, beam) for n in list(u.PROTOTYPES) + list(u.PLAIN)}
+print('typed', sys.argv[1])
+'''
+
+
+def test_units_are_typed_in_both_import_orders():
+    """A unit imported before the library is loaded is typed by load(); one imported after it is typed by its register call.  Fresh
+    child processes: this one has long imported everything.  No GPU is touched: loading the library and setting argtypes
+    initialises nothing."""
+    import __graft_entry__ as g
+    g.build()
+    for order in ('import-first', 'load-first'):
+        r = subprocess.run([sys.executable, '-c', _ORDER_CHILD, order], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True)
+        assert r.returncode == 0 and f'typed {order}' in r.stdout, r.stdout + r.stderr
+
+
+def test_untyped_call_is_refused():
+    from lcasr_amd.hip import _lib
+    with pytest.raises(RuntimeError, match='sconf_version_no_such'):
+        _lib.call('sconf_version_no_such')
+    with pytest.raises(RuntimeError, match='sconf_num_cus_no_such'):
+        _lib.call('sconf_num_cus_no_such', 1, 2)
+
+
+def test_double_registration_is_refused():
+    from lcasr_amd.hip import _lib, beam
+    with pytest.raises(ValueError, match='sconf_beam_ctc'):
+        _lib.register(beam.PROTOTYPES, {})
+    with pytest.raises(ValueError, match='sconf_version'):
+        _lib.register({}, {'sconf_version': ([], ctypes.c_int)})
+    with pytest.raises(ValueError, match='sconf_new_a'):
+        _lib.register({'sconf_new_a': []}, {'sconf_new_a': ([], ctypes.c_int)})
+    assert 'sconf_new_a' not in _lib.bound() and not any('sconf_new_a' in t for u in _lib._units for t in u)
 
 
 def test_host_side_argument_validation_sets_error():

@@ -27,14 +27,7 @@ def ops():
 def _check(ops, id, monkeypatch):
     for k in SWITCHES: monkeypatch.delenv(k, raising=False)
     if id in FC.MFMA_OFF: monkeypatch.setenv('SCONF_SUB_MFMA', '0')
-    case = FC.build(id, ops._lib.load())
-    try:
-        figures = FP.run_case(case, 'cuda')
-    except RuntimeError as e:                        # a launch refused on the host is a failure of this case; a device fault ends the
-        if 'HIP error' in str(e) or 'illegal memory access' in str(e):            # session: nothing more runs on a faulted GPU
-            pytest.exit(f'{id}: device fault, no further case is launched: {e}', returncode=3)
-        raise
-    print(FP.report_line(case, figures))
+    FP.run_on_device(FC.build(id, ops._lib.load()), ops._lib.PROTOTYPES)
 
 
 @pytest.mark.parametrize('id', FC.ids_of('gemm128'))
