@@ -2,8 +2,12 @@
 
 What the reference's evaluation drivers run through pyctcdecode (`build_ctcdecoder(vocab, kenlm_model_path=None, alpha=None,
 beta=None)` and `decode_beams`, lcasr/eval/utils.py:14-43), as the textbook two-score prefix search on the GPU (csrc/beam.hip through
-hip/beam.py; include/sconf_beam.h holds the exact contract).  pyctcdecode's word-level merging and every kind of LM fusion are not
-part of it: `lm_score` equals `logit_score`."""
+hip/beam.py; include/sconf_beam.h holds the exact contract).  Without a language model `lm_score` equals `logit_score`.
+
+With `lm=` (a decoding.lm.NGramLM, token-level) the search is the fused one of include/sconf_lm.h (csrc/beam_lm.hip through
+hip/lm.py): every created token adds alpha ln P(token | LM context) + beta to its prefix's ranking key, as pyctcdecode's
+`build_ctcdecoder(vocab, kenlm_model_path, alpha, beta)` does per unit.  pyctcdecode's word-level merging, word-level and neural LMs,
+hotwords and </s> scoring are not part of it."""
 from __future__ import annotations
 
 from typing import Callable, List, NamedTuple, Optional, Tuple
@@ -43,6 +47,42 @@ def ctc_beam_search(log_probs: torch.Tensor, input_lengths=None, blank: int = 0,
     return CTCBeams(*(t[0] for t in out)) if single else CTCBeams(*out)
 
 
+class CTCBeamsLM(NamedTuple):
+    """CTCBeams of a search with a language model: scores are the ranking keys (acoustic log-probability + the LM's bonus), best
+    first; logit_scores (B, nbest) f64 the acoustic log-probabilities of the same hypotheses."""
+    count: torch.Tensor
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    token_frames: torch.Tensor
+    scores: torch.Tensor
+    logit_scores: torch.Tensor
+
+
+def ctc_beam_search_lm(log_probs: torch.Tensor, lm, alpha: float = 0.5, beta: float = 1.5, input_lengths=None, blank: int = 0,
+                       beam_width: int = 100, nbest: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0,
+                       max_tokens_per_frame: int = 16, max_len: Optional[int] = None) -> CTCBeamsLM:
+    """ctc_beam_search with the n-gram LM `lm` (decoding.lm.NGramLM) fused in: a created token adds alpha ln P(token | context) + beta
+    to its prefix's key.  The other options, the class padding and the shapes are those of ctc_beam_search."""
+    if lm is None:
+        raise ValueError('ctc_beam_search_lm needs a language model; ctc_beam_search is the search without one')
+    from ..hip import lm as lm_kernels               # the fifth ABI unit: bound only when an LM is used
+    single = log_probs.dim() == 2
+    if log_probs.dim() not in (2, 3):
+        raise ValueError(f'log_probs must be (N, C) or (B, N, C), got {tuple(log_probs.shape)}')
+    lp = (log_probs[None] if single else log_probs).float()
+    if lm.num_tokens > lp.shape[-1]:
+        raise ValueError(f'the LM has {lm.num_tokens} tokens, log_probs have {lp.shape[-1]} classes')
+    pad = -lp.shape[-1] % 4
+    if pad:
+        lp = torch.nn.functional.pad(lp, (0, pad), value=float('-inf'))
+    lp = lp.contiguous()
+    il = None if input_lengths is None else torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    out = lm_kernels.ctc_beam_lm(lp, il, lm.device_image(lp.device), lm.n_states, lm.n_entries, lm.num_tokens, lm.order, lm.start_state,
+                                 int(blank), int(beam_width), int(nbest), float(token_min_logp), float(beam_prune_logp),
+                                 int(max_tokens_per_frame), int(lp.shape[1] if max_len is None else max_len), float(alpha), float(beta))
+    return CTCBeamsLM(*(t[0] for t in out)) if single else CTCBeamsLM(*out)
+
+
 class OutputBeam(NamedTuple):
     """One hypothesis, with the field names of pyctcdecode's OutputBeam that the reference's drivers read."""
     text: str
@@ -67,16 +107,19 @@ def _word_groups(ids: List[int], tokenizer, word_start: Optional[Callable[[int],
 
 class BeamSearchCTCDecoder(torch.nn.Module):
     """GreedyCTCDecoder's interface over the beam search; `decode_beams` is pyctcdecode's.  Search options (beam_width, nbest,
-    token_min_logp, beam_prune_logp, max_tokens_per_frame, max_len) are those of ctc_beam_search; word_start as in word_timestamps."""
+    token_min_logp, beam_prune_logp, max_tokens_per_frame, max_len) are those of ctc_beam_search; word_start as in word_timestamps.
+    lm (a decoding.lm.NGramLM) with alpha, beta: the fused search of ctc_beam_search_lm; lm=None: the search without an LM."""
 
-    def __init__(self, tokenizer=None, blank_id=0, word_start: Optional[Callable[[int], bool]] = None, **search_options):
+    def __init__(self, tokenizer=None, blank_id=0, word_start: Optional[Callable[[int], bool]] = None, lm=None, alpha: float = 0.5,
+                 beta: float = 1.5, **search_options):
         super().__init__()
         self.tokenizer = tokenizer
         self.blank = blank_id
         self.word_start = word_start
         self.options = dict(search_options)
+        self.lm, self.alpha, self.beta = lm, float(alpha), float(beta)
 
-    def _search(self, emission, **override) -> CTCBeams:
+    def _search(self, emission, **override):
         if not torch.is_tensor(emission):
             emission = torch.as_tensor(emission)
         if emission.dim() != 2:
@@ -86,6 +129,8 @@ class BeamSearchCTCDecoder(torch.nn.Module):
         opts = {**self.options, **{k: v for k, v in override.items() if v is not None}}
         if 'nbest' in opts and 'beam_width' in opts:
             opts['nbest'] = min(opts['nbest'], opts['beam_width'])
+        if self.lm is not None:
+            return ctc_beam_search_lm(emission, self.lm, self.alpha, self.beta, blank=self.blank, **opts)
         return ctc_beam_search(emission, blank=self.blank, **opts)
 
     def forward(self, emission: torch.Tensor, decode=True):
@@ -102,10 +147,12 @@ class BeamSearchCTCDecoder(torch.nn.Module):
         return self.tokenizer.decode(ids) if decode else ids
 
     def decode_beams(self, logits, beam_width: Optional[int] = None) -> List[OutputBeam]:
-        """The hypotheses of `logits` (num_seq, num_label), best first: .text, .tokens, .logit_score, .lm_score (= logit_score: there
-        is no LM) and .text_frames = [(word, (first frame, last token's frame + 1))]."""
+        """The hypotheses of `logits` (num_seq, num_label), best first: .text, .tokens, .logit_score (the acoustic log-probability),
+        .lm_score (the ranking key: logit_score plus the LM's alpha ln P + beta per token; = logit_score without an LM) and
+        .text_frames = [(word, (first frame, last token's frame + 1))]."""
         out = self._search(logits, beam_width=beam_width)
         count, lengths, scores = int(out.count), out.lengths.tolist(), out.scores.tolist()
+        logit = out.logit_scores.tolist() if self.lm is not None else scores
         tokens, frames = out.tokens.cpu(), out.token_frames.cpu()
         beams = []
         for r in range(count):
@@ -115,5 +162,5 @@ class BeamSearchCTCDecoder(torch.nn.Module):
             spell = (lambda g: self.tokenizer.decode([ids[k] for k in g]).strip()) if self.tokenizer is not None else (lambda g: str(ids[g[0]]))
             text_frames = [(spell(g), (fr[g[0]], fr[g[-1]] + 1)) for g in groups]
             text = self.tokenizer.decode(ids) if self.tokenizer is not None else ' '.join(str(i) for i in ids)
-            beams.append(OutputBeam(text, ids, scores[r], scores[r], text_frames))
+            beams.append(OutputBeam(text, ids, logit[r], scores[r], text_frames))
         return beams

@@ -30,14 +30,19 @@ from .wer import word_error_rate_detail
 MODES = ('averaged_moving_window', 'buffered', 'windowed_attention')
 
 
-def _decoder(model, tokenizer, beam_width: int):
-    """beam_width 1: the greedy decoder (per-frame argmax); above: prefix beam search without a language model."""
+def _decoder(model, tokenizer, beam_width: int, lm=None, alpha: float = 0.5, beta: float = 1.5):
+    """beam_width 1: the greedy decoder (per-frame argmax); above: prefix beam search, with the n-gram LM `lm` (decoding.lm.NGramLM)
+    fused in if one is given."""
     if beam_width < 1:
         raise ValueError(f'beam_width must be at least 1, got {beam_width}')
     blank = model.decoder.num_classes - 1
     if beam_width == 1:
+        if lm is not None:
+            raise ValueError('a language model needs a beam search: beam_width must be above 1 (the greedy decoder takes no LM)')
         return GreedyCTCDecoder(tokenizer=tokenizer, blank_id=blank)
-    return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width)
+    if lm is None:
+        return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width)
+    return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
 
 
 class _Args:
@@ -73,15 +78,17 @@ def _evaluation_mode(model, evaluation_mode: str, seq_len: int, args):
 
 def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
              evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
-             include_per_recording_evaluations: bool = False, args=None, beam_width: int = 1) -> List[dict]:
+             include_per_recording_evaluations: bool = False, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5,
+             beta: float = 1.5) -> List[dict]:
     """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
     of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last.
-    beam_width > 1 decodes with decoding.beam.BeamSearchCTCDecoder instead of the per-frame argmax."""
+    beam_width > 1 decodes with decoding.beam.BeamSearchCTCDecoder instead of the per-frame argmax; lm (a decoding.lm.NGramLM) with
+    alpha, beta fuses an n-gram language model into that search."""
     args = _Args() if args is None else args
     normalize = (lambda s: s) if normalize is None else normalize
     all_texts, all_golds, wer_data = [], [], []
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
-        decoder = _decoder(model, tokenizer, beam_width)
+        decoder = _decoder(model, tokenizer, beam_width, lm, alpha, beta)
         for rec_id, spec, gold_text in recordings:
             logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer,
                              use_tqdm=False, return_numpy=False)
@@ -98,16 +105,16 @@ def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeniz
 
 
 def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
-               normalise: bool = True, args=None, beam_width: int = 1) -> str:
+               normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5) -> str:
     """Waveform to transcript: 16 kHz waveform (L,) or (channels, L) on the GPU -> spectrogram (utils.audio_tools.to_spectogram of
-    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search.  The text is
-    returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
+    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search, with the n-gram LM `lm`
+    fused in if one is given.  The text is returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
     args = _Args() if args is None else args
     spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
                          return_numpy=False)
-        return _decoder(model, tokenizer, beam_width)(logits)
+        return _decoder(model, tokenizer, beam_width, lm, alpha, beta)(logits)
 
 
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True):
