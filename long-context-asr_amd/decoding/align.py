@@ -2,7 +2,8 @@
 
 `ctc_forced_align` is what torchaudio.functional.forced_align computes - the most probable frame path that collapses to the
 transcript - for batches with ragged lengths, run on the GPU (csrc/align.hip through hip/align.py; include/sconf_align.h holds the
-exact contract).  `word_timestamps` turns token spans into the word-level {'word', 'startTime', 'endTime'} records from which the
+exact contract).  A transcript of more than 8191 labels - a whole recording - goes through the long form of the same contract
+(csrc/align_long.hip through hip/align_long.py, include/sconf_align_long.h), up to 65535 labels.  `word_timestamps` turns token spans into the word-level {'word', 'startTime', 'endTime'} records from which the
 reference's loader cuts per-chunk targets (lcasr/utils/dataloading.py:28-57)."""
 from __future__ import annotations
 
@@ -11,6 +12,8 @@ from typing import Callable, List, NamedTuple, Optional
 import torch
 
 from ..hip import align as align_kernels          # the HIP op layer (tests swap align_kernels.ctc_align for the numpy restatement)
+
+SHORT_FORM_LABELS = 8191                           # sconf_align_max_labels(): routing below it needs no library (the tests hold it to the query)
 
 
 class CTCAlignment(NamedTuple):
@@ -25,7 +28,8 @@ class CTCAlignment(NamedTuple):
 
 
 def ctc_forced_align(log_probs: torch.Tensor, targets, input_lengths=None, target_lengths=None, blank: int = 0) -> CTCAlignment:
-    """log_probs (N, C) or (B, N, C) log-probabilities; targets (S,) or (B, Smax) token ids (tensor or list); lengths (B,) or None."""
+    """log_probs (N, C) or (B, N, C) log-probabilities; targets (S,) or (B, Smax) token ids (tensor or list); lengths (B,) or None.
+    A batch of up to 8191 labels per row runs on the short unit, a wider one of up to 65535 on the long unit; more raises ValueError."""
     single = log_probs.dim() == 2
     if log_probs.dim() not in (2, 3):
         raise ValueError(f'log_probs must be (N, C) or (B, N, C), got {tuple(log_probs.shape)}')
@@ -37,7 +41,14 @@ def ctc_forced_align(log_probs: torch.Tensor, targets, input_lengths=None, targe
     if tg.dim() != 2 or tg.shape[0] != lp.shape[0]:
         raise ValueError(f'targets must be (S,) or (B, Smax) with B = {lp.shape[0]}, got {tuple(tg.shape)}')
     as_len = lambda v: None if v is None else torch.as_tensor(v).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-    out = align_kernels.ctc_align(lp, tg.contiguous(), as_len(input_lengths), as_len(target_lengths), int(blank))
+    op = align_kernels.ctc_align
+    if tg.shape[1] > SHORT_FORM_LABELS:
+        from ..hip import align_long as long_kernels  # the sixth ABI unit: bound only when a transcript needs it
+        if tg.shape[1] > long_kernels.MAX_LABELS:
+            raise ValueError(f'ctc_forced_align: {tg.shape[1]} labels: at most {long_kernels.MAX_LABELS} '
+                             f'(a lattice of {2 * long_kernels.MAX_LABELS + 1} states) are supported')
+        op = long_kernels.ctc_align
+    out = op(lp, tg.contiguous(), as_len(input_lengths), as_len(target_lengths), int(blank))
     return CTCAlignment(*(t[0] for t in out)) if single else CTCAlignment(*out)
 
 

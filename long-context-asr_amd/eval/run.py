@@ -128,7 +128,8 @@ def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap
     """Word timestamps of a known transcript: log-probs of spec (1, F, T) exactly as `evaluate` computes them in `evaluation_mode`,
     CTC forced alignment of tokenizer.encode(text) on the GPU, then decoding.align.word_timestamps - a list of
     {'word', 'startTime', 'endTime', 'logp'} with times in the reference's '12.34s' form (one frame of the log-probs is
-    subsampling_factor * HOP_LENGTH / SR seconds).  Raises ValueError when the transcript has more labels than the frames can emit."""
+    subsampling_factor * HOP_LENGTH / SR seconds).  Raises ValueError when the transcript has more labels than the frames can emit.
+    A transcript of up to 65535 labels is taken: a whole recording (from 8192 labels on through the long form of the aligner)."""
     args = _Args() if args is None else args
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
