@@ -5,6 +5,7 @@ Mirrors the reference package layout for this path only:
   lcasr_amd.components.*                          <->  lcasr/components/{attention,convolution,batchrenorm,
                                                        fused_dense,normalisation,wrappers,decoder,subsampling,rotary_emb}.py
   lcasr_amd.losses.CTCLoss                        <->  torch.nn.CTCLoss as used by exp/train.py:104,249
+  lcasr_amd.losses.wctc_loss, WCTCLoss            <->  lcasr/losses/wctc.py (wild-card CTC: soft, max_prob, sum_prob)
   lcasr_amd.optim.MADGRAD                         <->  lcasr/optim/madgrad.py
   lcasr_amd.hip                                   ->   ctypes binding of libsconf_hip.so (include/sconf.h)
 """

@@ -22,6 +22,7 @@ import torch
 from torch.autograd import Function
 
 from .hip import ops
+from .hip import wctc as _wctc
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -869,3 +870,62 @@ def ctc_nll(log_probs_bnc, targets, input_lengths, target_lengths, blank: int) -
         log_probs_bnc = torch.nn.functional.pad(log_probs_bnc, (0, 4 - _C % 4), value=-1e30)
     tg, il, tl = _ctc_int_args(dev, targets, input_lengths, target_lengths)
     return CTCFn.apply(log_probs_bnc, tg, il, tl, blank)
+
+
+# =================================================================================================
+# W-CTC  — the reference's lcasr/losses/wctc.py (wctc_loss / WCTCLoss) seam, csrc/wctc.hip
+# =================================================================================================
+class WCTCFn(Function):
+    @staticmethod
+    def forward(ctx, log_probs_bnc, targets, input_lengths, target_lengths, blank: int, mode: str):
+        lp = log_probs_bnc.contiguous()
+        nll, ws = _wctc.wctc_fwd(lp, targets, input_lengths, target_lengths, blank, mode)
+        ctx.save_for_backward(ws, targets, input_lengths, target_lengths)       # the log-probs are not read again: the workspace has their gather
+        ctx.blank, ctx.mode, ctx.shape = blank, mode, tuple(lp.shape)
+        return nll
+
+    @staticmethod
+    def backward(ctx, dnll):
+        ws, targets, input_lengths, target_lengths = ctx.saved_tensors
+        g = _wctc.wctc_bwd(ctx.shape, ws, targets, input_lengths, target_lengths, dnll.contiguous().to(F32), ctx.blank, ctx.mode)
+        return g, None, None, None, None, None
+
+
+def _wctc_rows(targets, target_lengths, B: int):
+    """1-D concatenated targets -> (B, max length) rows padded with -1 (the lengths must be on the host, as in the reference's loop)."""
+    if target_lengths.is_cuda:
+        raise ValueError('W-CTC: 1-D concatenated targets need target_lengths on the host')
+    tls = [int(v) for v in target_lengths]
+    if len(tls) != B or any(v < 0 for v in tls) or sum(tls) > targets.numel():
+        raise ValueError('W-CTC: target_lengths do not fit the concatenated targets')
+    rows = torch.full((B, max(tls + [1])), -1, dtype=targets.dtype, device=targets.device)
+    at = 0
+    for b, n in enumerate(tls):
+        rows[b, :n] = targets[at:at + n]
+        at += n
+    return rows
+
+
+def wctc_nll(log_probs_bnc, targets, input_lengths, target_lengths, blank: int, mode: str = 'soft') -> torch.Tensor:
+    """Per-sample wild-card CTC losses (B,) from batch-major (B,N,C) f32 log-probs, mode 'soft' | 'max_prob' | 'sum_prob'
+    (include/sconf_wctc.h).  targets (B,Smax), entries past target_lengths may be negative padding, or 1-D concatenated with
+    target_lengths on the host.  As ctc_nll, bad arguments raise when the tensors are on the host and poison the sample (NaN) when
+    they are on the device; an empty transcript (target_length 0) is such an argument here."""
+    _wctc.mode_id(mode)
+    dev = log_probs_bnc.device
+    _B, _N, _C = log_probs_bnc.shape
+    if targets.dim() == 1:
+        targets = _wctc_rows(targets, target_lengths, _B)
+    if not target_lengths.is_cuda and target_lengths.numel() and int(target_lengths.min()) < 1:
+        raise ValueError('W-CTC: target_lengths must be at least 1 (an empty transcript has no last label to track)')
+    if targets.shape[1] > _wctc.MAX_LABELS:
+        raise ValueError(f'W-CTC: {targets.shape[1]} labels per sample: at most {_wctc.MAX_LABELS} are supported')
+    labels = targets
+    if not targets.is_cuda:                                  # padding past target_lengths is no label: keep it out of the range check
+        pad = targets < 0 if target_lengths.is_cuda else torch.arange(targets.shape[1])[None, :] >= target_lengths[:, None]
+        labels = targets.masked_fill(pad, 0)
+    _check_ctc_host_args(labels, input_lengths, target_lengths, _N, _C)
+    if _C % 4:                                            # the kernels move 4 classes per access: pad with impossible classes (p = 0)
+        log_probs_bnc = torch.nn.functional.pad(log_probs_bnc, (0, 4 - _C % 4), value=-1e30)
+    tg, il, tl = _ctc_int_args(dev, targets, input_lengths, target_lengths)
+    return WCTCFn.apply(log_probs_bnc, tg, il, tl, int(blank), mode)

@@ -34,12 +34,21 @@ def synthetic_batch(B: int, T: int, vocab_size: int, seed: int = 0, device='cuda
 
 class Trainer:
     def __init__(self, model, lr: float = 3e-3, clip_value: float = 0.8, global_batch: Optional[int] = None,
-                 bucket_bytes: int = 64 << 20, fused_loss: bool = True, spec_augment=None):
+                 bucket_bytes: int = 64 << 20, fused_loss: bool = True, spec_augment=None, wildcard: Optional[str] = None):
         """fused_loss: run the decoder head and the CTC loss as one operator (model(..., ctc_targets=...)); False keeps the
         reference's two calls (posteriors, then CTCLoss) - same loss and gradients, 25 GB more HBM traffic per step at B = 128.
         spec_augment: optional module applied as spec_augment(audio, lengths) to every batch before the forward
         (utils.augmentation.SpecAugment; exp/train.py:64-68,227).  The epoch / warm-up gate stays with the caller, who passes or
-        withholds the module; None = no augmentation."""
+        withholds the module; None = no augmentation.
+        wildcard: None = plain CTC (every frame is explained by the transcript).  'soft' | 'max_prob' | 'sum_prob' = the wild-card
+        CTC loss of that mode (losses.wctc_loss) for chunks whose transcripts miss the chunk's first or last frames; it takes the
+        unfused path (posteriors, then Fn.wctc_nll).  A fused head + W-CTC operator does not exist (out of scope), so
+        fused_loss=True is refused with it: pass fused_loss=False."""
+        if wildcard is not None:
+            Fn._wctc.mode_id(wildcard)
+            if fused_loss:
+                raise ValueError("Trainer: wildcard needs fused_loss=False: there is no fused decoder-head + W-CTC operator")
+        self.wildcard = wildcard
         self.model = model
         self.spec_augment = spec_augment
         self.fused_loss = fused_loss
@@ -59,6 +68,9 @@ class Trainer:
             audio = self.spec_augment(audio, lengths)
         if self.fused_loss:                              # head + log_softmax + CTC as one operator: the posteriors are never written
             loss = self.model(audio, length=lengths, ctc_targets=(targets, target_lengths))['ctc_nll'].sum()
+        elif self.wildcard is not None:                  # posteriors, then the wild-card loss of the chosen mode
+            out = self.model(audio, length=lengths)
+            loss = Fn.wctc_nll(out['final_posteriors'], targets, out['length'], target_lengths, self.ctc.blank, self.wildcard).sum()
         else:
             out = self.model(audio, length=lengths)
             loss = self.ctc(out['final_posteriors'].transpose(0, 1), targets, out['length'], target_lengths)
