@@ -1,5 +1,6 @@
 """Evaluation driver — the per-recording loop of eval/run.py:71-125 of the reference without its dataset loading; `transcribe` and
-`spectrograms_of` put the audio front end (utils/audio_tools.py) before it, so that a 16 kHz waveform is enough.
+`spectrograms_of` put the audio front end (utils/audio_tools.py) before it, so that a waveform is enough: at 16 kHz, or at the rate it
+was decoded at (`sample_rate`), resampled on the device.
 
 Four steps per recording, as there: log-probs in one of three modes, CTC decoding (greedy, or beam search for beam_width > 1), text normalisation, and
 word_error_rate_detail.  The modes are the reference's `--evaluation_mode` choices (run.py:37-44):
@@ -22,7 +23,7 @@ import torch
 from ..decoding.align import ctc_forced_align, word_timestamps
 from ..decoding.beam import BeamSearchCTCDecoder
 from ..decoding.greedy import GreedyCTCDecoder
-from ..utils.audio_tools import HOP_LENGTH, SR, grab_left_channel, to_spectogram
+from ..utils.audio_tools import HOP_LENGTH, SR, grab_left_channel, resample, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
 from .utils import fetch_logits as moving_average_eval
 from .wer import word_error_rate_detail
@@ -104,23 +105,33 @@ def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeniz
     return wer_data
 
 
+def _left_at_16k(waveform: torch.Tensor, sample_rate: int) -> torch.Tensor:
+    """(1, L') left channel at 16 kHz: as it is, or through the resampler in one pass."""
+    if sample_rate == SR:
+        return grab_left_channel(waveform)
+    return resample(waveform, sample_rate, SR, mix='left')
+
+
 def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
-               normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5) -> str:
-    """Waveform to transcript: 16 kHz waveform (L,) or (channels, L) on the GPU -> spectrogram (utils.audio_tools.to_spectogram of
-    the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search, with the n-gram LM `lm`
+               normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
+               sample_rate: int = SR) -> str:
+    """Waveform to transcript: waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz (16 kHz, or any rate
+    utils.audio_tools.resample takes: its left channel is resampled to 16 kHz on the device first) -> spectrogram
+    (utils.audio_tools.to_spectogram of the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search, with the n-gram LM `lm`
     fused in if one is given.  The text is returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
     args = _Args() if args is None else args
-    spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
                          return_numpy=False)
         return _decoder(model, tokenizer, beam_width, lm, alpha, beta)(logits)
 
 
-def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True):
-    """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time."""
+def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR):
+    """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time; waveforms
+    at `sample_rate` Hz, resampled to 16 kHz on the device where that is another rate."""
     for rec_id, waveform, gold_text in recordings:
-        yield rec_id, to_spectogram(grab_left_channel(waveform), global_normalisation=normalise), gold_text
+        yield rec_id, to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise), gold_text
 
 
 def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
@@ -142,7 +153,8 @@ def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap
 
 
 def align_waveform(model, waveform: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int,
-                   evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None) -> List[dict]:
-    """`align` from a 16 kHz waveform (L,) or (channels, L) on the GPU: the spectrogram of the left channel in front, as `transcribe`."""
-    spec = to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
+                   evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None, sample_rate: int = SR) -> List[dict]:
+    """`align` from a waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz: the spectrogram of the left channel (resampled to
+    16 kHz where the rate is another) in front, as `transcribe`."""
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise)
     return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args)
