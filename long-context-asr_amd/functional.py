@@ -510,8 +510,9 @@ class ConvBlockFn(Function):
         dw2 = _wgrad(dy16, y2, pw2)
         db2 = _bgrad(dy16, pb2, colsum=dycs)
         ddw, dbdw, dbrnw, dbrnb = _G(pwdw, wdw2.shape), _G(pbdw), _G(pbrnw), _G(pbrnb)
-        dg, dgcs = ops.convmod_bwd(dy2, hc, g, lengths, wdw2, brn_w, coef, B, N, training, BRN_EPS, ddw.t, dbdw.t, dbrnw.t, dbrnb.t,
-                                   colsum=pb1 is not None)
+        dg = ops.convmod_bwd(dy2, hc, g, lengths, wdw2, brn_w, coef, B, N, training, BRN_EPS, ddw.t, dbdw.t, dbrnw.t, dbrnb.t,
+                             colsum=pb1 is not None)
+        dg, dgcs = dg if pb1 is not None else (dg, None)                              # (the column sums come back only when asked for)
         dw1 = _wgrad(dg, h, pw1)
         db1 = _bgrad(dg, pb1, colsum=dgcs)
         dh = ops.gemm(dg, w1t, 'nt')
