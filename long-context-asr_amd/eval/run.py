@@ -16,14 +16,15 @@ from __future__ import annotations
 
 import contextlib
 import math
-from typing import Callable, Iterable, List, Optional, Tuple
+from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
 from ..decoding.align import ctc_forced_align, word_timestamps
 from ..decoding.beam import BeamSearchCTCDecoder
 from ..decoding.greedy import GreedyCTCDecoder
-from ..utils.audio_tools import HOP_LENGTH, SR, grab_left_channel, resample, to_spectogram
+from ..hip import noise as noiser
+from ..utils.audio_tools import HOP_LENGTH, SR, add_background_noise, add_gaussian_snr, grab_left_channel, resample, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
 from .utils import fetch_logits as moving_average_eval
 from .wer import word_error_rate_detail
@@ -105,33 +106,79 @@ def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeniz
     return wer_data
 
 
-def _left_at_16k(waveform: torch.Tensor, sample_rate: int) -> torch.Tensor:
-    """(1, L') left channel at 16 kHz: as it is, or through the resampler in one pass."""
-    if sample_rate == SR:
-        return grab_left_channel(waveform)
-    return resample(waveform, sample_rate, SR, mix='left')
+def _left_at_16k(waveform: torch.Tensor, sample_rate: int, corrupt=None) -> torch.Tensor:
+    """(1, L') left channel at 16 kHz: as it is, or through the resampler in one pass; then through `corrupt`, a callable
+    (waveform, sample_rate=16000) -> waveform such as utils.augmentation.AddGaussianSNR, if one is given."""
+    left = grab_left_channel(waveform) if sample_rate == SR else resample(waveform, sample_rate, SR, mix='left')
+    return left if corrupt is None else corrupt(left, sample_rate=SR)
 
 
 def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
                normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
-               sample_rate: int = SR) -> str:
+               sample_rate: int = SR, corrupt=None) -> str:
     """Waveform to transcript: waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz (16 kHz, or any rate
-    utils.audio_tools.resample takes: its left channel is resampled to 16 kHz on the device first) -> spectrogram
+    utils.audio_tools.resample takes: its left channel is resampled to 16 kHz on the device first) -> `corrupt`, if given (a callable on the 16 kHz waveform:
+    utils.augmentation.AddGaussianSNR / AddBackgroundNoise, the reference's noise experiments) -> spectrogram
     (utils.audio_tools.to_spectogram of the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search, with the n-gram LM `lm`
     fused in if one is given.  The text is returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
     args = _Args() if args is None else args
-    spec = to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise)
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
                          return_numpy=False)
         return _decoder(model, tokenizer, beam_width, lm, alpha, beta)(logits)
 
 
-def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR):
+def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR, corrupt=None):
     """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time; waveforms
-    at `sample_rate` Hz, resampled to 16 kHz on the device where that is another rate."""
+    at `sample_rate` Hz, resampled to 16 kHz on the device where that is another rate, then through `corrupt` if one is given."""
     for rec_id, waveform, gold_text in recordings:
-        yield rec_id, to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise), gold_text
+        yield rec_id, to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise), gold_text
+
+
+def sweep_spectrograms(waveform: torch.Tensor, snrs: Sequence[float], noise='gaussian', seed: int = 17925, row: int = 0,
+                       normalise: bool = True, sample_rate: int = SR) -> torch.Tensor:
+    """(K, F, T): the spectrograms of one recording corrupted at each of the K levels of `snrs` - what snr_sweep feeds the model for
+    its recording number `row`.  The power is taken once per group of sconf_noise_max_levels levels, one launch mixes the group
+    and to_spectogram runs on the (K, L) batch; level k is bit-equal to to_spectogram of a separate add_gaussian_snr(x, snrs[k],
+    seed=seed, first_row=row) (add_background_noise(x, noise, snrs[k]))."""
+    if not (isinstance(noise, str) and noise == 'gaussian') and not (torch.is_tensor(noise) and noise.dim() == 1):
+        raise ValueError("noise must be 'gaussian' or a 1-D tensor (a 16 kHz clip)")
+    left = _left_at_16k(waveform, sample_rate)[0]
+    group = noiser.max_levels()
+    specs = []
+    for k0 in range(0, len(snrs), group):
+        levels = [float(s) for s in snrs[k0:k0 + group]]
+        mixed = add_gaussian_snr(left, levels, seed=seed, first_row=row) if isinstance(noise, str) else add_background_noise(left, noise, levels)
+        specs.append(to_spectogram(mixed, global_normalisation=normalise))
+    return specs[0] if len(specs) == 1 else torch.cat(specs)
+
+
+def snr_sweep(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int, snrs: Sequence[float],
+              noise='gaussian', seed: int = 17925, normalise: bool = True, sample_rate: int = SR, **evaluate_keywords) -> List[dict]:
+    """WER against SNR: `evaluate` over `recordings`, (id, waveform, gold_text) triples with the waveform (L,) or (channels, L) on the
+    GPU, once per level of `snrs` (dB), the left channel at 16 kHz corrupted at that level before the spectrogram.
+    noise: 'gaussian' - recording n gets the normals of (seed, row id n), the same sequence at every level as the reference's
+    per-file re-seeding gives them - or a 1-D device tensor, a 16 kHz background clip that starts at 0 and repeats.
+    Per recording the waveform's power is taken once and ONE launch mixes all the levels (sweep_spectrograms; in groups of
+    sconf_noise_max_levels where there are more); to_spectogram runs on the (K, L) batch and each level then goes the way of `evaluate`, whose keywords
+    (evaluation_mode, normalize, args, beam_width, lm, alpha, beta) pass through.
+    Returns one record per level, in the order of `snrs`: {'snr_db', 'wer', 'words', 'ins_rate', 'del_rate', 'sub_rate'}."""
+    snrs = [float(s) for s in snrs]
+    if not snrs:
+        raise ValueError('snr_sweep: no SNR levels')
+    if 'include_per_recording_evaluations' in evaluate_keywords:
+        raise ValueError('snr_sweep returns one record per level: include_per_recording_evaluations is not taken')
+    per_level = [[] for _ in snrs]
+    for n, (rec_id, waveform, gold_text) in enumerate(recordings):
+        specs = sweep_spectrograms(waveform, snrs, noise, seed, n, normalise, sample_rate)
+        for k in range(len(snrs)):
+            per_level[k].append((rec_id, specs[k:k + 1], gold_text))
+    records = []
+    for snr, recs in zip(snrs, per_level):
+        total = evaluate(model, recs, tokenizer, seq_len, overlap, **evaluate_keywords)[-1]
+        records.append({'snr_db': snr, **{key: total[key] for key in ('wer', 'words', 'ins_rate', 'del_rate', 'sub_rate')}})
+    return records
 
 
 def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
@@ -153,8 +200,9 @@ def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap
 
 
 def align_waveform(model, waveform: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int,
-                   evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None, sample_rate: int = SR) -> List[dict]:
+                   evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None, sample_rate: int = SR,
+                   corrupt=None) -> List[dict]:
     """`align` from a waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz: the spectrogram of the left channel (resampled to
-    16 kHz where the rate is another) in front, as `transcribe`."""
-    spec = to_spectogram(_left_at_16k(waveform, sample_rate), global_normalisation=normalise)
+    16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `transcribe`."""
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args)

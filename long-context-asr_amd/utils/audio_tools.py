@@ -8,8 +8,12 @@ the STFT nor a padded copy of the waveform reaches memory.
 rolloff 0.99), a polyphase windowed-sinc filter, as one HIP kernel (csrc/resample.hip through hip/resample.py): the filter is
 evaluated here on the host in f64, cast to f32 as torchaudio does, and handed to the device as a compact table of the taps that
 are not clamped to zero; the left channel or the channel mean is taken while the waveform is read, once.  `processing_chain` takes
-the decoded waveform and its sample rate: 16 kHz as it is, any other rate with resample_input=True.  Decoding audio files stays on
-the host and outside this package."""
+the decoded waveform and its sample rate: 16 kHz as it is, any other rate with resample_input=True.
+
+`wave_power`, `add_gaussian_snr` and `add_background_noise` are the corruptions of the reference's noise-robustness drivers
+(audiomentations' AddGaussianSNR and AddBackgroundNoise; csrc/noise.hip through hip/noise.py) between `resample` and `to_spectogram`:
+the mean square of every row in one pass, then one launch that mixes all the SNR levels asked for from one noise sequence.
+Decoding audio files stays on the host and outside this package."""
 from __future__ import annotations
 
 import math
@@ -18,6 +22,7 @@ from typing import Optional
 import torch
 
 from ..hip import audio
+from ..hip import noise as noiser
 from ..hip import resample as resampler
 
 WIN_LENGTH = 400
@@ -215,12 +220,118 @@ def total_frames(seconds: float) -> int:
     return int((seconds * 16000) / HOP_LENGTH)
 
 
-def processing_chain(waveform: torch.Tensor, sample_rate: int, normalise: bool = True, resample_input: bool = False) -> torch.Tensor:
+def _noise_rows(waveform: torch.Tensor, lengths, what: str):
+    """((rows, L) view with unit stride along L, lengths (rows,) int64 on the device or None)."""
+    if waveform.dim() not in (1, 2):
+        raise ValueError('Waveform must be 1D or 2D')
+    if waveform.dtype != torch.float32:
+        raise TypeError(f'{what}: waveform must be float32, got {waveform.dtype}')
+    if waveform.shape[-1] < 1 or waveform.shape[0] < 1:
+        raise ValueError(f'{what}: empty waveform {tuple(waveform.shape)}')
+    wave = waveform[None] if waveform.dim() == 1 else waveform
+    if wave.stride(1) != 1:
+        wave = wave.contiguous()
+    return wave, _row_counts(lengths, wave.shape[0], 0, wave.shape[1], wave.device, what, 'lengths')
+
+
+def _row_counts(v, rows: int, lo: int, hi: int, device, what: str, name: str):
+    """None, or `rows` integers as an int64 device vector; a host-given one must lie in lo..hi."""
+    if v is None:
+        return None
+    v = torch.as_tensor(v)
+    if tuple(v.shape) != (rows,) or v.dtype.is_floating_point:
+        raise ValueError(f'{what}: {name} must be {rows} integers')
+    if not v.is_cuda and (int(v.min()) < lo or int(v.max()) > hi):
+        raise ValueError(f'{what}: every one of {name} must be in {lo}..{hi}')
+    return v.to(device=device, dtype=torch.int64).contiguous()
+
+
+def _snr_levels(snr_db, rows: int, device, what: str):
+    """snr_db as the (rows, K) f32 device tensor of a launch, and whether it was a single number (no level axis in the result).
+    A number, a sequence of K numbers shared by the rows, or a (rows, K) tensor; NaN in a host-given value is refused."""
+    single = not torch.is_tensor(snr_db) and not hasattr(snr_db, '__len__')
+    t = torch.as_tensor([snr_db] if single else snr_db)
+    if torch.is_tensor(snr_db) and snr_db.dim() == 2:
+        if snr_db.shape[0] != rows:
+            raise ValueError(f'{what}: snr_db of shape {tuple(snr_db.shape)} for {rows} rows')
+    elif t.dim() != 1:
+        raise ValueError(f'{what}: snr_db must be a number, a sequence of K numbers or a (rows, K) tensor')
+    if not 1 <= t.shape[-1] <= noiser.max_levels():
+        raise ValueError(f'{what}: {t.shape[-1]} SNR levels; a call takes 1..{noiser.max_levels()} (sconf_noise_max_levels)')
+    if not t.is_cuda and bool(torch.isnan(t.double()).any()):
+        raise ValueError(f'{what}: snr_db holds NaN')
+    t = t.to(device=device, dtype=torch.float32)
+    return (t[None].expand(rows, -1) if t.dim() == 1 else t).contiguous(), single
+
+
+def _shaped(out: torch.Tensor, waveform: torch.Tensor, single: bool) -> torch.Tensor:
+    """(rows, K, L) -> the input's shape for a single level, (K, L) for a 1-D input."""
+    out = out[:, 0] if single else out
+    return out[0] if waveform.dim() == 1 else out
+
+
+def wave_power(waveform: torch.Tensor, lengths=None) -> torch.Tensor:
+    """Mean square of every row, f64 (rows,) on the device ((1,) for a 1-D waveform): waveform (L,) or (rows, L) f32 on the GPU; with
+    lengths (rows,) over the first lengths[b] samples of row b, 0 for an empty row.  Exact squares summed in f64 in a fixed order:
+    the same bits on every call, and for a row of a batch the bits of the row alone."""
+    wave, lengths = _noise_rows(waveform, lengths, 'wave_power')
+    return noiser.power(wave, lengths)
+
+
+def add_gaussian_snr(waveform: torch.Tensor, snr_db, lengths=None, seed: int = 17925, first_row: int = 0, first_sample: int = 0) -> torch.Tensor:
+    """audiomentations' AddGaussianSNR at a set SNR, on the device: y = x + sigma z with sigma = sqrt(mean x^2) 10^(-snr_db / 20) per
+    row.  waveform (L,) or (rows, L) f32 on the GPU.  snr_db: a number -> the input's shape; a sequence of K numbers shared by the
+    rows or a (rows, K) tensor -> (rows, K, L), or (K, L) for a 1-D input, every level from the SAME standard normals z (as the
+    reference's per-file re-seeding gives them), in one launch.
+    z is a function of (seed, first_row + row, first_sample + i) alone (include/sconf_noise.h): a row of a batch gets the noise it
+    would get alone with first_row = its index, a piece of a recording the noise of the whole with first_sample = its start.
+    lengths: (rows,) sample counts of a padded batch; the power is taken over them and samples behind them are 0.  A silent row,
+    or snr_db = +inf, returns the input bit for bit."""
+    wave, lengths = _noise_rows(waveform, lengths, 'add_gaussian_snr')
+    snr, single = _snr_levels(snr_db, wave.shape[0], wave.device, 'add_gaussian_snr')
+    out = noiser.add_gaussian(wave, lengths, noiser.power(wave, lengths), snr, int(seed), int(first_row), int(first_sample))
+    return _shaped(out, waveform, single)
+
+
+def add_background_noise(waveform: torch.Tensor, noise: torch.Tensor, snr_db, lengths=None, noise_lengths=None, offsets=None) -> torch.Tensor:
+    """audiomentations' AddBackgroundNoise at a set SNR, on the device: y = x + g v, v[i] = noise[(offset + i) mod its length] - the clip
+    cropped at `offsets` where it is longer than the row, repeated where it is shorter - and g = sqrt(mean x^2 / mean v^2)
+    10^(-snr_db / 20), the clip's mean square over the samples actually used.  A clip with an rms below 1e-9 leaves the input as it
+    is, bit for bit, and so does a silent row.
+    noise: (NL,) or (1, NL) f32 on the GPU, one clip for all rows, or (rows, NL), one per row; noise_lengths and offsets (one per
+    clip, one per row; tensors or sequences) default to NL and 0.  snr_db, lengths and the result's shape as for add_gaussian_snr."""
+    wave, lengths = _noise_rows(waveform, lengths, 'add_background_noise')
+    rows = wave.shape[0]
+    if noise.dim() not in (1, 2) or noise.dtype != torch.float32 or noise.shape[-1] < 1:
+        raise TypeError('add_background_noise: noise must be a non-empty (NL,) or (clips, NL) float32 tensor')
+    clip = noise[None] if noise.dim() == 1 else noise
+    if clip.shape[0] not in (1, rows):
+        raise ValueError(f'add_background_noise: {clip.shape[0]} clips for {rows} rows; one clip or one per row')
+    if clip.stride(1) != 1:
+        clip = clip.contiguous()
+    NL = clip.shape[1]
+    noise_lengths = _row_counts(noise_lengths, clip.shape[0], 1, NL, wave.device, 'add_background_noise', 'noise_lengths')
+    if noise_lengths is None:
+        noise_lengths = torch.full((clip.shape[0],), NL, dtype=torch.int64, device=wave.device)
+    offsets = _row_counts(offsets, rows, 0, NL - 1, wave.device, 'add_background_noise', 'offsets')      # the kernel wraps one past its clip
+    snr, single = _snr_levels(snr_db, rows, wave.device, 'add_background_noise')
+    p_noise = noiser.power(clip, lengths, noise_lengths, offsets, L=wave.shape[1], B=rows)
+    out = noiser.add_background(wave, lengths, clip, noise_lengths, offsets, noiser.power(wave, lengths), p_noise, snr)
+    return _shaped(out, waveform, single)
+
+
+def processing_chain(waveform: torch.Tensor, sample_rate: int, normalise: bool = True, resample_input: bool = False, corrupt=None) -> torch.Tensor:
     """The reference's chain from the decoded file on: left channel, resampled to 16 kHz, then the spectrogram (1, 80, T).  The
-    resampling step is taken only with resample_input=True; without it any rate but 16 kHz is refused, as before."""
+    resampling step is taken only with resample_input=True; without it any rate but 16 kHz is refused, as before.
+    corrupt: a callable (waveform (1, L) at 16 kHz, sample_rate=16000) -> waveform of that shape, applied before the spectrogram - an
+    utils.augmentation.AddGaussianSNR, say, where the reference's noise experiments corrupt the file."""
     if sample_rate != SR:
         if not resample_input:
             raise NotImplementedError(f'processing_chain: sample rate {sample_rate} Hz; pass resample_input=True to resample to {SR} Hz '
                                       f'on the device')
-        return to_spectogram(resample(waveform, sample_rate, SR, mix='left'), global_normalisation=normalise)
-    return to_spectogram(grab_left_channel(waveform), global_normalisation=normalise)
+        left = resample(waveform, sample_rate, SR, mix='left')
+    else:
+        left = grab_left_channel(waveform)
+    if corrupt is not None:
+        left = corrupt(left, sample_rate=SR)
+    return to_spectogram(left, global_normalisation=normalise)

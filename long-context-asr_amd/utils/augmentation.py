@@ -20,14 +20,22 @@ INTERVAL LAW.  torchaudio is not available where this was written; the law below
     interval [floor(min_value), floor(min_value) + floor(value))
 
 so a mask is at most mask_param' wide and lies inside the axis.  Bit-equal random streams with torchaudio are not a goal.
+
+AddGaussianSNR and AddBackgroundNoise are the two waveform corruptions of the reference's noise-robustness drivers
+(eval/rev16_gaussian_noise/run.py, eval/rev16_background_noise/run.py), with audiomentations' constructor keywords and call
+signature and the mixing on the device (utils/audio_tools.py: add_gaussian_snr, add_background_noise).  What a call draws - whether
+it applies, the SNR, the clip and where it starts - comes from a random.Random(seed) on the host, in that order; nothing is read
+back from the device.  Bit-equal noise with numpy's generator is not a goal: the normals are the contract of include/sconf_noise.h.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import random
+from typing import Optional, Sequence, Tuple
 
 import torch
 
 from .. import functional as Fn          # Fn.ops: the HIP op layer (tests swap it for the CPU kernel references)
+from . import audio_tools
 
 
 class SpecAugment(torch.nn.Module):
@@ -105,3 +113,72 @@ class SpecAugment(torch.nn.Module):
         Fn.ops.require_gpu(specgram, 'specgram')
         t_iv, f_iv = self.draw(specgram.shape, generator, specgram.device)
         return self.apply(specgram, t_iv, f_iv, self.mask_value(specgram, audio_lengths))
+
+
+class _SNRTransform:
+    """What the two corruptions share: the keywords, the host generator and the draw of `apply or not` and of the SNR."""
+
+    def __init__(self, min_snr_db: float, max_snr_db: float, p: float, seed: Optional[int]) -> None:
+        if min_snr_db > max_snr_db:
+            raise ValueError(f'min_snr_db = {min_snr_db} must not exceed max_snr_db = {max_snr_db}')
+        if not 0 <= p <= 1:
+            raise ValueError(f'p = {p} must be within [0, 1]')
+        self.min_snr_db, self.max_snr_db, self.p = float(min_snr_db), float(max_snr_db), float(p)
+        self.rng = random.Random(seed)
+        self.calls = 0                                                     # applied calls so far: the row id of the next one's normals
+
+    def draw_snr(self) -> Optional[float]:
+        """None where this call leaves the waveform alone, else the SNR in dB."""
+        if self.rng.random() >= self.p:
+            return None
+        return self.rng.uniform(self.min_snr_db, self.max_snr_db)
+
+
+class AddGaussianSNR(_SNRTransform):
+    """audiomentations.AddGaussianSNR(min_snr_db, max_snr_db, p) on the device.  The normals' key is `seed` (17925, the reference's
+    per-file numpy seed, where None) and the n-th applied call takes row id n of them, so that successive files get different noise
+    and a transform rebuilt with the same seed repeats it."""
+
+    def __init__(self, min_snr_db: float = 5.0, max_snr_db: float = 40.0, p: float = 0.5, seed: Optional[int] = None) -> None:
+        super().__init__(min_snr_db, max_snr_db, p, seed)
+        self.noise_seed = 17925 if seed is None else int(seed)
+
+    def __call__(self, waveform: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        snr = self.draw_snr()
+        if snr is None:
+            return waveform
+        rows = 1 if waveform.dim() == 1 else waveform.shape[0]
+        out = audio_tools.add_gaussian_snr(waveform, snr, seed=self.noise_seed, first_row=self.calls)
+        self.calls += rows
+        return out
+
+
+class AddBackgroundNoise(_SNRTransform):
+    """audiomentations.AddBackgroundNoise(sounds, min_snr_db, max_snr_db, p) on the device.  `sounds`: a list of 1-D float32 device
+    tensors at 16 kHz (decoding files stays with the caller).  Per applied call one clip is chosen; where it is longer than the
+    waveform it is cropped at a drawn offset in 0 .. len(clip) - len(waveform), where it is not it starts at 0 and repeats."""
+
+    def __init__(self, sounds: Sequence[torch.Tensor], min_snr_db: float = 3.0, max_snr_db: float = 30.0, p: float = 0.5,
+                 seed: Optional[int] = None) -> None:
+        super().__init__(min_snr_db, max_snr_db, p, seed)
+        self.sounds = list(sounds)
+        if not self.sounds or any(not torch.is_tensor(s) or s.dim() != 1 or s.shape[0] < 1 for s in self.sounds):
+            raise ValueError('sounds must be a non-empty list of non-empty 1-D tensors')
+
+    def draw(self, length: int) -> Optional[Tuple[float, int, int]]:
+        """(snr_db, index of the clip, offset into it) of one call on a waveform of `length` samples, or None."""
+        snr = self.draw_snr()
+        if snr is None:
+            return None
+        which = self.rng.randrange(len(self.sounds))
+        spare = self.sounds[which].shape[0] - length
+        return snr, which, self.rng.randint(0, spare) if spare > 0 else 0
+
+    def __call__(self, waveform: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        drawn = self.draw(waveform.shape[-1])
+        if drawn is None:
+            return waveform
+        snr, which, offset = drawn
+        rows = 1 if waveform.dim() == 1 else waveform.shape[0]
+        self.calls += rows
+        return audio_tools.add_background_noise(waveform, self.sounds[which], snr, offsets=[offset] * rows)
