@@ -32,19 +32,23 @@ from .wer import word_error_rate_detail
 MODES = ('averaged_moving_window', 'buffered', 'windowed_attention')
 
 
-def _decoder(model, tokenizer, beam_width: int, lm=None, alpha: float = 0.5, beta: float = 1.5):
+def _decoder(model, tokenizer, beam_width: int, lm=None, alpha: float = 0.5, beta: float = 1.5, hotwords=None, hotword_weight: float = 10.0):
     """beam_width 1: the greedy decoder (per-frame argmax); above: prefix beam search, with the n-gram LM `lm` (decoding.lm.NGramLM)
-    fused in if one is given."""
+    fused in if one is given, and `hotwords` (a list of strings or a decoding.hotwords.HotwordSet) boosted by hotword_weight inside
+    the search if any are given."""
     if beam_width < 1:
         raise ValueError(f'beam_width must be at least 1, got {beam_width}')
     blank = model.decoder.num_classes - 1
     if beam_width == 1:
         if lm is not None:
             raise ValueError('a language model needs a beam search: beam_width must be above 1 (the greedy decoder takes no LM)')
+        if hotwords is not None:
+            raise ValueError('hotwords need a beam search: beam_width must be above 1 (greedy decoding cannot boost: it keeps one path)')
         return GreedyCTCDecoder(tokenizer=tokenizer, blank_id=blank)
+    hot = {} if hotwords is None else dict(hotwords=hotwords, hotword_weight=hotword_weight)
     if lm is None:
-        return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width)
-    return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
+        return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width, **hot)
+    return BeamSearchCTCDecoder(tokenizer=tokenizer, blank_id=blank, beam_width=beam_width, lm=lm, alpha=alpha, beta=beta, **hot)
 
 
 class _Args:
@@ -81,16 +85,17 @@ def _evaluation_mode(model, evaluation_mode: str, seq_len: int, args):
 def evaluate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
              evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None,
              include_per_recording_evaluations: bool = False, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5,
-             beta: float = 1.5) -> List[dict]:
+             beta: float = 1.5, hotwords=None, hotword_weight: float = 10.0) -> List[dict]:
     """WER of `model` over recordings, an iterable of (id, spec (1, F, T), gold_text).  Returns the reference's wer_data: a list
     of dicts recording / wer / words / ins_rate / del_rate / sub_rate, one per recording if asked for, and 'all' last.
     beam_width > 1 decodes with decoding.beam.BeamSearchCTCDecoder instead of the per-frame argmax; lm (a decoding.lm.NGramLM) with
-    alpha, beta fuses an n-gram language model into that search."""
+    alpha, beta fuses an n-gram language model into that search; hotwords (a list of strings or a decoding.hotwords.HotwordSet) with
+    hotword_weight boosts them inside it (pyctcdecode's decode_beams keywords)."""
     args = _Args() if args is None else args
     normalize = (lambda s: s) if normalize is None else normalize
     all_texts, all_golds, wer_data = [], [], []
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
-        decoder = _decoder(model, tokenizer, beam_width, lm, alpha, beta)
+        decoder = _decoder(model, tokenizer, beam_width, lm, alpha, beta, hotwords, hotword_weight)
         for rec_id, spec, gold_text in recordings:
             logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer,
                              use_tqdm=False, return_numpy=False)
@@ -115,18 +120,18 @@ def _left_at_16k(waveform: torch.Tensor, sample_rate: int, corrupt=None) -> torc
 
 def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
                normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
-               sample_rate: int = SR, corrupt=None) -> str:
+               sample_rate: int = SR, corrupt=None, hotwords=None, hotword_weight: float = 10.0) -> str:
     """Waveform to transcript: waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz (16 kHz, or any rate
     utils.audio_tools.resample takes: its left channel is resampled to 16 kHz on the device first) -> `corrupt`, if given (a callable on the 16 kHz waveform:
     utils.augmentation.AddGaussianSNR / AddBackgroundNoise, the reference's noise experiments) -> spectrogram
     (utils.audio_tools.to_spectogram of the left channel) -> log-probs in `evaluation_mode` -> greedy CTC decoding (beam_width 1) or prefix beam search, with the n-gram LM `lm`
-    fused in if one is given.  The text is returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
+    fused in if one is given and `hotwords` (a list of strings or a decoding.hotwords.HotwordSet) boosted by hotword_weight inside it if any are given.  The text is returned as decoded (evaluate's `normalize` and lower() belong to scoring)."""
     args = _Args() if args is None else args
     spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
                          return_numpy=False)
-        return _decoder(model, tokenizer, beam_width, lm, alpha, beta)(logits)
+        return _decoder(model, tokenizer, beam_width, lm, alpha, beta, hotwords, hotword_weight)(logits)
 
 
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR, corrupt=None):
@@ -162,7 +167,7 @@ def snr_sweep(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeni
     per-file re-seeding gives them - or a 1-D device tensor, a 16 kHz background clip that starts at 0 and repeats.
     Per recording the waveform's power is taken once and ONE launch mixes all the levels (sweep_spectrograms; in groups of
     sconf_noise_max_levels where there are more); to_spectogram runs on the (K, L) batch and each level then goes the way of `evaluate`, whose keywords
-    (evaluation_mode, normalize, args, beam_width, lm, alpha, beta) pass through.
+    (evaluation_mode, normalize, args, beam_width, lm, alpha, beta, hotwords, hotword_weight) pass through.
     Returns one record per level, in the order of `snrs`: {'snr_db', 'wer', 'words', 'ins_rate', 'del_rate', 'sub_rate'}."""
     snrs = [float(s) for s in snrs]
     if not snrs:
