@@ -15,6 +15,7 @@ to the identity (`.lower()` is applied as in the reference)."""
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
@@ -22,6 +23,8 @@ import torch
 
 from ..decoding.align import ctc_forced_align, word_timestamps
 from ..decoding.beam import BeamSearchCTCDecoder
+from ..decoding.confidence import (ConfidenceConfig, frame_confidence, greedy_confidence, spans_from_token_frames, token_confidence,
+                                   word_confidence)
 from ..decoding.greedy import GreedyCTCDecoder
 from ..hip import noise as noiser
 from ..utils.audio_tools import HOP_LENGTH, SR, add_background_noise, add_gaussian_snr, grab_left_channel, resample, to_spectogram
@@ -134,6 +137,41 @@ def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: 
         return _decoder(model, tokenizer, beam_width, lm, alpha, beta, hotwords, hotword_weight)(logits)
 
 
+def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
+                      normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
+                      sample_rate: int = SR, corrupt=None, hotwords=None, hotword_weight: float = 10.0,
+                      confidence: ConfidenceConfig = ConfidenceConfig()) -> dict:
+    """`transcribe` with what it knows about its answer: {'text', 'tokens', 'token_confidence', 'words': [{'word', 'startTime',
+    'endTime', 'confidence'}]}, the times in word_timestamps' '12.34s' form.  The keywords are transcribe's; `confidence` (a
+    decoding.confidence.ConfidenceConfig) chooses the measure and the aggregations.  beam_width 1: greedy decoding, a token's
+    confidence over its run of frames and the blanks behind it (without them if exclude_blank), its times from its own run.
+    beam_width > 1: the best beam, the LM and the hotwords acting inside the search as in transcribe; token i covers the frames from
+    its own to the next token's, a word lasts from its first token's frame to one past its last token's.  Frame, token and word
+    confidences are computed on the device (include/sconf_confid.h)."""
+    args = _Args() if args is None else args
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                         return_numpy=False)
+        decoder = _decoder(model, tokenizer, beam_width, lm, alpha, beta, hotwords, hotword_weight)
+    blank = model.decoder.num_classes - 1
+    if beam_width == 1:
+        g = greedy_confidence(logits, blank, confidence)
+        ids, conf, times = g.tokens, g.token_confidence, [s[:2] for s in g.spans]
+    else:
+        out = decoder._search(logits, nbest=1)
+        n = min(int(out.lengths[0]), out.tokens.shape[-1]) if int(out.count) else 0
+        frames = out.token_frames[0, :n]
+        idx, frame_conf = frame_confidence(logits, confidence)
+        conf = token_confidence(frame_conf, idx, spans_from_token_frames(frames, logits.shape[0]), confidence, blank).tolist() if n else []
+        ids, times = out.tokens[0, :n].tolist(), [[f, f + 1] for f in frames.tolist()]
+    word_start = getattr(decoder, 'word_start', None)
+    words = word_timestamps(ids, times, tokenizer, model.subsampling.subsampling_factor * HOP_LENGTH / SR, word_start=word_start)
+    for w, c in zip(words, word_confidence(ids, conf, tokenizer, confidence, word_start)):
+        w['confidence'] = c
+    return {'text': tokenizer.decode(ids), 'tokens': ids, 'token_confidence': conf, 'words': words}
+
+
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR, corrupt=None):
     """(id, waveform, gold_text) -> the (id, spec (1, F, T), gold_text) triples `evaluate` takes, one recording at a time; waveforms
     at `sample_rate` Hz, resampled to 16 kHz on the device where that is another rate, then through `corrupt` if one is given."""
@@ -187,12 +225,15 @@ def snr_sweep(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeni
 
 
 def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
-          args=None) -> List[dict]:
+          args=None, confidence: Optional[ConfidenceConfig] = None) -> List[dict]:
     """Word timestamps of a known transcript: log-probs of spec (1, F, T) exactly as `evaluate` computes them in `evaluation_mode`,
     CTC forced alignment of tokenizer.encode(text) on the GPU, then decoding.align.word_timestamps - a list of
     {'word', 'startTime', 'endTime', 'logp'} with times in the reference's '12.34s' form (one frame of the log-probs is
     subsampling_factor * HOP_LENGTH / SR seconds).  Raises ValueError when the transcript has more labels than the frames can emit.
-    A transcript of up to 65535 labels is taken: a whole recording (from 8192 labels on through the long form of the aligner)."""
+    A transcript of up to 65535 labels is taken: a whole recording (from 8192 labels on through the long form of the aligner).
+    confidence (a decoding.confidence.ConfidenceConfig): each record gains 'confidence', the word's confidence from the frame
+    confidences over the alignment's own token spans (every frame of a span is the token's, so none is excluded as blank); None: the
+    records of today."""
     args = _Args() if args is None else args
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
@@ -201,13 +242,19 @@ def align(model, spec: torch.Tensor, text: str, tokenizer, seq_len: int, overlap
     al = ctc_forced_align(logits, ids, blank=model.decoder.num_classes - 1)
     if not math.isfinite(float(al.score)):
         raise ValueError(f'transcript of {len(ids)} labels cannot be emitted in {logits.shape[0]} frames')
-    return word_timestamps(ids, al.spans, tokenizer, model.subsampling.subsampling_factor * HOP_LENGTH / SR, token_logp=al.token_logp)
+    words = word_timestamps(ids, al.spans, tokenizer, model.subsampling.subsampling_factor * HOP_LENGTH / SR, token_logp=al.token_logp)
+    if confidence is not None:
+        idx, frame_conf = frame_confidence(logits, confidence)
+        conf = token_confidence(frame_conf, None, al.spans[:len(ids)], dataclasses.replace(confidence, exclude_blank=False))
+        for w, c in zip(words, word_confidence(ids, conf, tokenizer, confidence)):
+            w['confidence'] = c
+    return words
 
 
 def align_waveform(model, waveform: torch.Tensor, text: str, tokenizer, seq_len: int, overlap: int,
                    evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, args=None, sample_rate: int = SR,
-                   corrupt=None) -> List[dict]:
+                   corrupt=None, confidence: Optional[ConfidenceConfig] = None) -> List[dict]:
     """`align` from a waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz: the spectrogram of the left channel (resampled to
     16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `transcribe`."""
     spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
-    return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args)
+    return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args, confidence=confidence)
