@@ -1,8 +1,9 @@
-// What csrc/align.hip (one lattice per workgroup, up to 8191 labels) and csrc/align_long.hip (the lattice cut into state slabs, up to
-// 65535 labels) share: the workspace pitches, the emission gather, the emission loads of the lattice step, the walk back and the two
-// output kernels.  An internal header: everything sits in an anonymous namespace, so each of the two files instantiates its own copy
-// (the kernels have internal linkage).  All of it indexes the lattice by its GLOBAL state over the whole 2 Smax + 1, so none of it
-// knows whether one workgroup or a chain of slab launches filled the back-pointers.
+// What csrc/align.hip (one lattice per workgroup, up to 8191 labels), csrc/align_long.hip (the lattice cut into state slabs, up to
+// 65535 labels) and csrc/seg.hip (either of them with a star label) share: the workspace pitches, the emission gather, the emission
+// loads of the lattice step, the walk back, the two output kernels and their launches.  An internal header: everything sits in an
+// anonymous namespace, so each of the files instantiates its own copy (the kernels have internal linkage).  All of it indexes the
+// lattice by its GLOBAL state over the whole 2 Smax + 1, so none of it knows whether one workgroup or a chain of slab launches
+// filled the back-pointers.
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -25,9 +26,12 @@ inline int walk_window() {
 
 // One workgroup per (sample, frame) row: the frame's log-probs go to LDS with 16-byte loads, the S + 1 emissions are gathered from
 // there (ctc_gather_kernel's scheme).  Frames at or past the sample's length are never read by the lattice and are not written.
+// STAR (csrc/seg.hip): the label value C is the star, whose cell is `star_logp` at every frame; the row that is read stays C wide.
+template <bool STAR>
 __global__ __launch_bounds__(256) void align_gather_kernel(const float* __restrict__ lp, const int* __restrict__ targets,
                                                            const int* __restrict__ in_len, const int* __restrict__ tg_len,
-                                                           float* __restrict__ em, int B, int N, int C, int Smax, int LP, int blank) {
+                                                           float* __restrict__ em, int B, int N, int C, int Smax, int LP, int blank,
+                                                           float star_logp) {
     extern __shared__ float row[];                      // [C]
     const int E = LP + 4;
     for (long bt = blockIdx.x; bt < (long)B * N; bt += gridDim.x) {
@@ -41,7 +45,11 @@ __global__ __launch_bounds__(256) void align_gather_kernel(const float* __restri
         float* out = em + bt * E;
         for (int j = threadIdx.x; j < E; j += 256) {
             float v = 0.f;
-            if (j < S) v = row[min(max(targets[(long)b * Smax + j], 0), C - 1)];   // an out-of-range label poisons the sample; never index with it
+            if (j < S) {
+                const int lab = targets[(long)b * Smax + j];
+                v = row[min(max(lab, 0), C - 1)];       // an out-of-range label poisons the sample; never index with it
+                if (STAR && lab == C) v = star_logp;
+            }
             else if (j == LP) v = row[blank];
             out[j] = v;
         }
@@ -119,19 +127,43 @@ __global__ __launch_bounds__(256) void align_frames_kernel(const int* __restrict
     } else labels[o] = blank;
 }
 
+// STAR: a token whose label is C sums `star_logp` once per frame of its span instead of a log-prob.
+template <bool STAR>
 __global__ __launch_bounds__(256) void align_tokens_kernel(const float* __restrict__ lp, const int* __restrict__ targets,
                                                            const int* __restrict__ endst, const int* __restrict__ in_len,
                                                            const int* __restrict__ tg_len, int* __restrict__ spans, float* __restrict__ token_logp,
-                                                           int N, int C, int Smax) {
+                                                           int N, int C, int Smax, float star_logp) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     if (j >= Smax) return;
     const long o = (long)b * Smax + j;
     float sum = 0.f;
     if (endst[b] >= 0 && j < len_of(tg_len, b, Smax)) {
         const int lab = targets[o], f = spans[2 * o], l = min(spans[2 * o + 1], len_of(in_len, b, N));
-        if (f >= 0) for (int t = f; t < l; ++t) sum += lp[((long)b * N + t) * C + lab];       // (f < 0: only a path through non-finite log-probs skips a token)
+        if (STAR && lab == C) { if (f >= 0) for (int t = f; t < l; ++t) sum += star_logp; }
+        else if (f >= 0) for (int t = f; t < l; ++t) sum += lp[((long)b * N + t) * C + lab];  // (f < 0: only a path through non-finite log-probs skips a token)
     } else { spans[2 * o] = -1; spans[2 * o + 1] = -1; }
     token_logp[o] = sum;
+}
+
+// Steps 1 and 3 to 5 of a call as launches, the same for every lattice form.
+template <bool STAR>
+inline void launch_align_gather(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths, float* em,
+                                int64_t B, int64_t N, int64_t C, int64_t Smax, int LP, int blank, float star_logp, hipStream_t stream) {
+    hipLaunchKernelGGL(align_gather_kernel<STAR>, dim3((unsigned)std::min<long>(B * N, 65536)), dim3(256), (size_t)C * 4, stream, log_probs, targets,
+                       input_lengths, target_lengths, em, (int)B, (int)N, (int)C, (int)Smax, LP, blank, star_logp);
+}
+
+template <bool STAR>
+inline void launch_align_outputs(const float* log_probs, const int* targets, const int* input_lengths, const int* target_lengths,
+                                 const unsigned char* bp, const int* endst, int* path, int* labels, int* spans, float* token_logp, int64_t B,
+                                 int64_t N, int64_t C, int64_t Smax, int BPW, int blank, float star_logp, hipStream_t stream) {
+    hipLaunchKernelGGL(align_walk_kernel, dim3((unsigned)B), dim3(64), 0, stream, bp, endst, input_lengths, path, spans, (int)N, (int)Smax, BPW,
+                       walk_window());
+    hipLaunchKernelGGL(align_frames_kernel, dim3((unsigned)cdiv(N, 256), (unsigned)B), dim3(256), 0, stream, targets, endst, input_lengths,
+                       path, labels, spans, (int)N, (int)Smax, blank);
+    if (Smax > 0)
+        hipLaunchKernelGGL(align_tokens_kernel<STAR>, dim3((unsigned)cdiv(Smax, 256), (unsigned)B), dim3(256), 0, stream, log_probs, targets, endst,
+                           input_lengths, target_lengths, spans, token_logp, (int)N, (int)C, (int)Smax, star_logp);
 }
 
 }  // namespace

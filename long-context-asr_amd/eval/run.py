@@ -26,6 +26,7 @@ from ..decoding.beam import BeamSearchCTCDecoder
 from ..decoding.confidence import (ConfidenceConfig, frame_confidence, greedy_confidence, spans_from_token_frames, token_confidence,
                                    word_confidence)
 from ..decoding.greedy import GreedyCTCDecoder
+from ..decoding.segment import build_targets, ctc_segment, star_id
 from ..hip import noise as noiser
 from ..utils.audio_tools import HOP_LENGTH, SR, add_background_noise, add_gaussian_snr, grab_left_channel, resample, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
@@ -258,3 +259,50 @@ def align_waveform(model, waveform: torch.Tensor, text: str, tokenizer, seq_len:
     16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `transcribe`."""
     spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     return align(model, spec, text, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, args=args, confidence=confidence)
+
+
+def segment(model, spec: torch.Tensor, utterances: Sequence[str], tokenizer, seq_len: int, overlap: int,
+            evaluation_mode: str = 'averaged_moving_window', star_between: bool = True, star_ends: bool = True, star_logp: float = 0.0,
+            window: int = 30, min_confidence: Optional[float] = None, words: bool = False, args=None) -> List[dict]:
+    """CTC segmentation of a loose transcript: `utterances` are the texts of a recording in order, with unknown times; they may skip
+    parts of it (intros, music, adverts, cross-talk) and some may be wrong.  Log-probs of spec (1, F, T) exactly as `align` computes
+    them, then decoding.segment.ctc_segment over [*] u0 [*] u1 ... [*] on the GPU (blank = num_classes - 1, the star = num_classes).
+    Returns one {'text', 'startTime', 'endTime', 'confidence', 'logp'} per utterance, times in the '12.34s' form: 'logp' the mean
+    log-prob per frame of the utterance, 'confidence' its lowest mean over `window` consecutive frames (Kürzinger's
+    score_min_mean_over_L = 30, adopted, not tuned here).  min_confidence drops the records below it; words=True adds 'words', the
+    `word_timestamps` records of the utterance's tokens.  star_between / star_ends place the stars; star_logp = 0 lets a star also
+    take the cheap frames of the tokens beside it (they shrink towards one frame, as with torchaudio's <star>), a negative value
+    makes it win only over frames that match nothing; a star always takes at least one frame.  No value has been tuned on real
+    recordings here.  Raises ValueError when the row does not fit the frames, as `align` does."""
+    args = _Args() if args is None else args
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                         return_numpy=False)
+    ids = [[int(i) for i in tokenizer.encode(u)] for u in utterances]
+    C = model.decoder.num_classes
+    seg = ctc_segment(logits, ids, blank=C - 1, star_between=star_between, star_ends=star_ends, star_logp=star_logp, window=window)
+    if not math.isfinite(float(seg.alignment.score)):
+        raise ValueError(f'{len(ids)} utterances of {sum(len(u) for u in ids)} labels cannot be emitted in {logits.shape[0]} frames')
+    spf = model.subsampling.subsampling_factor * HOP_LENGTH / SR
+    ranges = build_targets(ids, star_id(C), star_between, star_ends)[1]
+    frames, logp, conf = seg.utt_frames.tolist(), seg.utt_logp.tolist(), seg.utt_conf.tolist()
+    spans, token_logp = seg.alignment.spans, seg.alignment.token_logp
+    records = []
+    for k, (text, (j0, j1)) in enumerate(zip(utterances, ranges)):
+        if min_confidence is not None and not conf[k] >= min_confidence:
+            continue
+        r = {'text': text, 'startTime': f'{frames[k][0] * spf:.2f}s', 'endTime': f'{frames[k][1] * spf:.2f}s', 'confidence': conf[k],
+             'logp': logp[k]}
+        if words:
+            r['words'] = word_timestamps(ids[k], spans[j0:j1], tokenizer, spf, token_logp=token_logp[j0:j1])
+        records.append(r)
+    return records
+
+
+def segment_waveform(model, waveform: torch.Tensor, utterances: Sequence[str], tokenizer, seq_len: int, overlap: int,
+                     evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, sample_rate: int = SR, corrupt=None,
+                     **kwargs) -> List[dict]:
+    """`segment` from a waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz: the spectrogram of the left channel (resampled
+    to 16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `align_waveform`."""
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
+    return segment(model, spec, utterances, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, **kwargs)
