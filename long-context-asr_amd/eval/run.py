@@ -306,3 +306,32 @@ def segment_waveform(model, waveform: torch.Tensor, utterances: Sequence[str], t
     to 16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `align_waveform`."""
     spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     return segment(model, spec, utterances, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, **kwargs)
+
+
+def search(model, spec: torch.Tensor, keywords, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
+           min_score_per_label: float = -0.5, max_hits: int = 64, args=None) -> List[dict]:
+    """Keyword search: where in the recording is each of `keywords` (a list of strings, or a decoding.kws.KeywordSet) said?
+    Log-probs of spec (1, F, T) exactly as `align` computes them, then decoding.kws.ctc_keyword_search on the GPU
+    (blank = num_classes - 1).  Returns one {'keyword', 'startTime', 'endTime', 'score'} per hit, times in the '12.34s' form, sorted
+    by start.  'score' is the total log-likelihood ratio of the keyword's best path over the span against the greedy path over the
+    same frames: 0 means the keyword IS the greedy decode of that span.  A keyword is reported from min_score_per_label times its
+    number of tokens on (the default is not tuned on real recordings; it is ignored for a KeywordSet, which carries its own).  A
+    keyword with more than max_hits hits carries 'truncated': True on its records."""
+    from ..decoding.kws import KeywordSet, ctc_keyword_search
+    args = _Args() if args is None else args
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                         return_numpy=False)
+    if not isinstance(keywords, KeywordSet):
+        keywords = KeywordSet.from_text(keywords, tokenizer, min_score_per_label=min_score_per_label)
+    hits = ctc_keyword_search(logits, keywords, blank=model.decoder.num_classes - 1, max_hits=max_hits)
+    return hits.records(model.subsampling.subsampling_factor * HOP_LENGTH / SR)
+
+
+def search_waveform(model, waveform: torch.Tensor, keywords, tokenizer, seq_len: int, overlap: int,
+                    evaluation_mode: str = 'averaged_moving_window', normalise: bool = True, sample_rate: int = SR, corrupt=None,
+                    **kwargs) -> List[dict]:
+    """`search` from a waveform (L,) or (channels, L) on the GPU at `sample_rate` Hz: the spectrogram of the left channel (resampled
+    to 16 kHz where the rate is another, then through `corrupt` if one is given) in front, as `align_waveform`."""
+    spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
+    return search(model, spec, keywords, tokenizer, seq_len, overlap, evaluation_mode=evaluation_mode, **kwargs)
