@@ -6,99 +6,12 @@
 // library's, and v != v must stay a NaN test.
 #include "common.h"
 #include "../../include/sconf_confid.h"
+#include "confid_measure.h"
 
 namespace {
 
-constexpr int QUADS = 4;                       // quads of four elements a lane of the register path holds at most
-constexpr int ROW_CAPACITY = 64 * QUADS * 4;   // 1024 classes in the registers of one wave
-constexpr int BLOCK = 256;
-constexpr int BLOCK_CAPACITY = BLOCK * QUADS * 4; // 4096 classes in the registers of one workgroup
 constexpr int SCAN_PER_THREAD = 4;
 constexpr int SCAN_CHUNK = BLOCK * SCAN_PER_THREAD;
-constexpr int NO_INDEX = 0x7fffffff;
-
-// what the host works out once per call: no division by alpha - 1 and no logarithm of V on the device
-struct Measure {
-    int method, norm;
-    float alpha;
-    float V;            // classes
-    float inv_vm1;      // 1 / (V - 1)
-    float inv_lnv;      // 1 / ln V
-    float inv_am1;      // 1 / (alpha - 1)                      (TSALLIS, RENYI)
-    float inv_hmax;     // 1 / H_max of TSALLIS
-    float e_hmax;       // e^-H_max of TSALLIS
-    float inv_1me;      // 1 / (1 - e^-H_max)
-};
-
-struct Best { float v; int i; };
-__device__ __forceinline__ void take(Best& b, float v, int i) { if (v > b.v || (v == b.v && i < b.i)) { b.v = v; b.i = i; } }
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(b.v, o, 64); const int oi = __shfl_xor(b.i, o, 64);
-        take(b, ov, oi);
-    }
-    return b;
-}
-
-// e^d for d <= 0 on the hardware's 2^x: the rounding of d log2(e) moves e^d by |d| e^d 2^-24 at most, which is below 2^-25 for every
-// d (the terms that carry a sum have small |d|), so the per-element exponential need not be the math library's
-__device__ __forceinline__ float exp_(float d) { return __builtin_amdgcn_exp2f(d * 1.4426950408889634f); }
-
-// the three sums of one element d = x - m <= 0 (or -inf): e^d, e^d d and e^(alpha d)
-struct Sums { float z, t, a; };
-template <int METHOD> __device__ __forceinline__ void add(Sums& s, float d, float alpha) {
-    const float e = exp_(d);
-    s.z += e;
-    if (METHOD == SCONF_CONFID_SHANNON) s.t += e > 0.f ? e * d : 0.f;                  // (0 * -inf is no part of the sum)
-    if (METHOD == SCONF_CONFID_TSALLIS || METHOD == SCONF_CONFID_RENYI) s.a += exp_(alpha * d);
-}
-
-template <int METHOD> __device__ __forceinline__ float confidence(const Sums& s, const Measure& q) {
-    if (METHOD == SCONF_CONFID_MAX_PROB) return (q.V / s.z - 1.f) * q.inv_vm1;
-    const float lnz = logf(s.z);
-    float H;
-    if (METHOD == SCONF_CONFID_SHANNON) H = lnz - s.t / s.z;
-    else {
-        const float ln_sa = logf(s.a) - q.alpha * lnz;
-        if (METHOD == SCONF_CONFID_RENYI) H = -ln_sa * q.inv_am1;
-        else {
-            H = (1.f - expf(ln_sa)) * q.inv_am1;
-            return q.norm == SCONF_CONFID_LIN ? 1.f - H * q.inv_hmax : (expf(-H) - q.e_hmax) * q.inv_1me;
-        }
-    }
-    return q.norm == SCONF_CONFID_LIN ? 1.f - H * q.inv_lnv : (q.V * expf(-H) - 1.f) * q.inv_vm1;
-}
-
-// a quad of four neighbouring elements from column c on: one 16-byte load where the row allows it, single elements elsewhere;
-// columns at and behind `classes` are never loaded and count as -inf
-__device__ __forceinline__ void load_quad(const float* __restrict__ xr, int c, int C, int vec, float (&v)[4]) {
-    if (vec && c + 4 <= C) load4(xr + c, v);
-    else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = c + e < C ? xr[c + e] : -INFINITY;
-    }
-}
-
-template <int G> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int G> __device__ __forceinline__ Best group_best(Best b) {
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(b.v, o, 64); const int oi = __shfl_xor(b.i, o, 64);
-        take(b, ov, oi);
-    }
-    return b;
-}
-template <int G> __device__ __forceinline__ bool group_any(bool f) {
-    int v = f;
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return v != 0;
-}
 
 // A row in the registers of G lanes (16: four rows per wave, for the short rows of a 129- or 144-class model, so that a wave has
 // several 16-byte loads per lane in flight; 64: one row per wave).  Lane g of the group holds the quads g, g + G, ... of four
@@ -306,8 +219,6 @@ __global__ __launch_bounds__(BLOCK) void aggregate_kernel(const float* __restric
     }
 }
 
-bool alpha_ok(float alpha) { return (alpha > 0.f && alpha < 1.f) || (alpha > 1.f && alpha <= 4.f); }
-
 template <int METHOD, int G, int NQ>
 void launch_group(const float* x, long M, int C, long stride, int vec, const Measure& q, int* idx, float* conf, hipStream_t st) {
     hipLaunchKernelGGL((frames_group_kernel<METHOD, G, NQ>), dim3((unsigned)cdiv(M, BLOCK / G)), dim3(BLOCK), 0, st, x, M, C, stride, vec, q, idx, conf);
@@ -346,14 +257,7 @@ SCONF_API int sconf_confid_frames(const float* x, int64_t M, int64_t classes, in
     else SCONF_REQUIRE(!with_alpha || alpha_ok(alpha), "sconf_confid_frames: alpha=%g must be in (0, 1), 1 or (1, 4]", (double)alpha);
     SCONF_REQUIRE(x && idx && conf, "sconf_confid_frames: null x, idx or conf");
     if (M == 0) return 0;
-    const double V = (double)classes, lnv = log(V);
-    Measure q{};
-    q.method = method; q.norm = norm; q.alpha = alpha;
-    q.V = (float)V; q.inv_vm1 = (float)(1.0 / (V - 1.0)); q.inv_lnv = (float)(1.0 / lnv);
-    if (method == SCONF_CONFID_TSALLIS || method == SCONF_CONFID_RENYI) {
-        const double am1 = (double)alpha - 1.0, hmax = (1.0 - exp(-am1 * lnv)) / am1;
-        q.inv_am1 = (float)(1.0 / am1); q.inv_hmax = (float)(1.0 / hmax); q.e_hmax = (float)exp(-hmax); q.inv_1me = (float)(1.0 / (1.0 - exp(-hmax)));
-    }
+    const Measure q = measure_of(method, norm, alpha, classes);
     const int vec = ((uintptr_t)x % 16 == 0) && row_stride % 4 == 0;
     switch (method) {
         case SCONF_CONFID_MAX_PROB: launch_frames<SCONF_CONFID_MAX_PROB>(x, M, (int)classes, row_stride, vec, q, idx, conf, stream); break;

@@ -9,7 +9,9 @@ argmax, one collapses the argmax vector into labels with their frames, one aggre
     g = greedy_confidence(log_probs, blank, cfg)              # tokens, spans, token_confidence, frame_confidence
     words = word_confidence(g.tokens, g.token_confidence, tokenizer, cfg)
 
-Not part of it: calibration against error labels, posterior (forward-backward) confidences, a temperature on the softmax."""
+`temperature=` on frame_confidence and greedy_confidence takes the confidences of softmax(log_probs / temperature) instead (through the
+temperature sweep of csrc/calib.hip with one temperature); decoding/calibration.py holds the calibration against error labels and the
+fit of that temperature.  Not part of it: posterior (forward-backward) confidences."""
 from __future__ import annotations
 
 import math
@@ -18,6 +20,7 @@ from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 
+from ..hip import calib as calib_kernels            # the temperature sweep, reached only where a temperature is given
 from ..hip import confid as confid_kernels          # the HIP op layer (tests swap its three ops for the numpy restatement)
 from .beam import _word_groups
 
@@ -85,10 +88,19 @@ def _on_device(t) -> torch.Tensor:
     return t
 
 
-def frame_confidence(log_probs: torch.Tensor, cfg: ConfidenceConfig = ConfidenceConfig(), classes: Optional[int] = None):
+def _inverse_temperature(temperature: float) -> torch.Tensor:
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f'temperature {temperature!r} must be finite and positive')
+    return torch.tensor([1.0 / t], dtype=torch.float64).to(torch.float32)
+
+
+def frame_confidence(log_probs: torch.Tensor, cfg: ConfidenceConfig = ConfidenceConfig(), classes: Optional[int] = None,
+                     temperature: Optional[float] = None):
     """log_probs (N, C) or (B, N, C): logits, log-probs or the log of averaged posteriors (the kernel normalises) -> (idx, conf) of
     shape (N,) or (B, N): the argmax (int32, first index on ties) and the confidence (f32) of every frame over the first `classes`
-    (default C) columns.  A frame with a NaN or without a finite score gives idx -1 and conf NaN."""
+    (default C) columns.  A frame with a NaN or without a finite score gives idx -1 and conf NaN.
+    temperature: the confidences of softmax(log_probs / temperature) (the argmax is the same); None: the call of today."""
     lp = _on_device(log_probs)
     if lp.dim() not in (2, 3):
         raise ValueError(f'log_probs must be (N, C) or (B, N, C), got {tuple(lp.shape)}')
@@ -97,7 +109,10 @@ def frame_confidence(log_probs: torch.Tensor, cfg: ConfidenceConfig = Confidence
     if rows.stride(-1) != 1:
         rows = rows.contiguous()
     method, norm = cfg.measure
-    idx, conf = confid_kernels.frames(rows, classes, method, norm, float(cfg.alpha))
+    if temperature is None:
+        idx, conf = confid_kernels.frames(rows, classes, method, norm, float(cfg.alpha))
+    else:
+        idx, conf = calib_kernels.frames_sweep(rows, _on_device(_inverse_temperature(temperature)), classes, method, norm, float(cfg.alpha))
     return idx.reshape(lp.shape[:-1]), conf.reshape(lp.shape[:-1])
 
 
@@ -120,11 +135,13 @@ def spans_from_token_frames(frames: torch.Tensor, T: int) -> torch.Tensor:
     return torch.stack([fr, end], dim=1).contiguous()
 
 
-def greedy_confidence(log_probs: torch.Tensor, blank: int, cfg: ConfidenceConfig = ConfidenceConfig(), lengths=None) -> GreedyConfidence:
-    """Greedy CTC decoding with confidences, in three launches and one copy to the host (frame_confidence stays on the device)."""
+def greedy_confidence(log_probs: torch.Tensor, blank: int, cfg: ConfidenceConfig = ConfidenceConfig(), lengths=None,
+                      temperature: Optional[float] = None) -> GreedyConfidence:
+    """Greedy CTC decoding with confidences, in three launches and one copy to the host (frame_confidence stays on the device).
+    temperature: as frame_confidence takes it; the tokens do not depend on it."""
     lp = _on_device(log_probs)
     single = lp.dim() == 2
-    idx, conf = frame_confidence(lp[None] if single else lp, cfg)
+    idx, conf = frame_confidence(lp[None] if single else lp, cfg, temperature=temperature)
     B, N = idx.shape
     il = None if lengths is None else torch.as_tensor(lengths).reshape(-1).to(device=idx.device, dtype=torch.int32).contiguous()
     targets, spans, tl = confid_kernels.runs(idx.contiguous(), il, int(blank), N)

@@ -22,7 +22,9 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import torch
 
 from ..decoding.align import ctc_forced_align, word_timestamps
-from ..decoding.beam import BeamSearchCTCDecoder
+from ..decoding import confidence as confidence_module
+from ..decoding.beam import BeamSearchCTCDecoder, _word_groups
+from ..decoding.calibration import calibration_metrics, fit_temperature, frame_confidence_sweep
 from ..decoding.confidence import (ConfidenceConfig, frame_confidence, greedy_confidence, spans_from_token_frames, token_confidence,
                                    word_confidence)
 from ..decoding.greedy import GreedyCTCDecoder
@@ -31,7 +33,7 @@ from ..hip import noise as noiser
 from ..utils.audio_tools import HOP_LENGTH, SR, add_background_noise, add_gaussian_snr, grab_left_channel, resample, to_spectogram
 from .buffered_transcription import fetch_logits as buffered_eval
 from .utils import fetch_logits as moving_average_eval
-from .wer import word_error_rate_detail
+from .wer import confusion_pairs, word_error_alignment, word_error_rate_detail
 
 MODES = ('averaged_moving_window', 'buffered', 'windowed_attention')
 
@@ -141,10 +143,11 @@ def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: 
 def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
                       normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
                       sample_rate: int = SR, corrupt=None, hotwords=None, hotword_weight: float = 10.0,
-                      confidence: ConfidenceConfig = ConfidenceConfig()) -> dict:
+                      confidence: ConfidenceConfig = ConfidenceConfig(), temperature: Optional[float] = None) -> dict:
     """`transcribe` with what it knows about its answer: {'text', 'tokens', 'token_confidence', 'words': [{'word', 'startTime',
     'endTime', 'confidence'}]}, the times in word_timestamps' '12.34s' form.  The keywords are transcribe's; `confidence` (a
-    decoding.confidence.ConfidenceConfig) chooses the measure and the aggregations.  beam_width 1: greedy decoding, a token's
+    decoding.confidence.ConfidenceConfig) chooses the measure and the aggregations; `temperature` (what `calibrate` chose, say) takes
+    the confidences of softmax(log_probs / temperature) and leaves the decoding as it is.  beam_width 1: greedy decoding, a token's
     confidence over its run of frames and the blanks behind it (without them if exclude_blank), its times from its own run.
     beam_width > 1: the best beam, the LM and the hotwords acting inside the search as in transcribe; token i covers the frames from
     its own to the next token's, a word lasts from its first token's frame to one past its last token's.  Frame, token and word
@@ -157,13 +160,13 @@ def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, ov
         decoder = _decoder(model, tokenizer, beam_width, lm, alpha, beta, hotwords, hotword_weight)
     blank = model.decoder.num_classes - 1
     if beam_width == 1:
-        g = greedy_confidence(logits, blank, confidence)
+        g = greedy_confidence(logits, blank, confidence, temperature=temperature)
         ids, conf, times = g.tokens, g.token_confidence, [s[:2] for s in g.spans]
     else:
         out = decoder._search(logits, nbest=1)
         n = min(int(out.lengths[0]), out.tokens.shape[-1]) if int(out.count) else 0
         frames = out.token_frames[0, :n]
-        idx, frame_conf = frame_confidence(logits, confidence)
+        idx, frame_conf = frame_confidence(logits, confidence, temperature=temperature)
         conf = token_confidence(frame_conf, idx, spans_from_token_frames(frames, logits.shape[0]), confidence, blank).tolist() if n else []
         ids, times = out.tokens[0, :n].tolist(), [[f, f + 1] for f in frames.tolist()]
     word_start = getattr(decoder, 'word_start', None)
@@ -171,6 +174,75 @@ def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, ov
     for w, c in zip(words, word_confidence(ids, conf, tokenizer, confidence, word_start)):
         w['confidence'] = c
     return {'text': tokenizer.decode(ids), 'tokens': ids, 'token_confidence': conf, 'words': words}
+
+
+def _word_confidence_sweep(logits: torch.Tensor, blank: int, temperatures: Sequence[float], cfg: ConfidenceConfig, tokenizer, word_start=None):
+    """The greedy words of logits (N, C) with their confidences at every temperature: (word texts, (K, words) f32 on the device).
+    One sweep launch for the frames, one collapse, and one aggregate launch each for tokens and words over all K rows at once
+    (row k of the (K, N) confidences is addressed by spans shifted by k N)."""
+    idx, conf = frame_confidence_sweep(logits, temperatures, cfg)
+    K, N = conf.shape
+    targets, spans, tl = confidence_module.confid_kernels.runs(idx[None].contiguous(), None, int(blank), N)
+    packed = torch.cat([tl, targets.reshape(-1)]).cpu()                                              # the one copy
+    n = int(packed[0])
+    ids = packed[1:1 + n].tolist()
+    if n == 0:
+        return [], torch.zeros(K, 0, dtype=torch.float32, device=conf.device)
+    shift = torch.arange(K, device=conf.device, dtype=torch.int32)[:, None, None]
+    frames = (spans[0, :n][:, (0, 2)][None] + shift * N).reshape(-1, 2).contiguous()
+    tok = confidence_module.confid_kernels.aggregate(conf.reshape(-1), frames, cfg.aggregation, idx.repeat(K) if cfg.exclude_blank else None, int(blank))
+    groups = _word_groups(ids, tokenizer, word_start)
+    first_last = torch.tensor([[g[0], g[-1] + 1] for g in groups], dtype=torch.int32).to(conf.device)
+    words = confidence_module.confid_kernels.aggregate(tok, (first_last[None] + shift * n).reshape(-1, 2).contiguous(), cfg.words, None, 0)
+    return [tokenizer.decode([ids[k] for k in g]) for g in groups], words.reshape(K, len(groups))
+
+
+def calibrate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
+              temperatures: Sequence[float] = (0.5, 0.67, 0.8, 1.0, 1.25, 1.5, 2.0, 3.0), confidence: ConfidenceConfig = ConfidenceConfig(),
+              evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None, args=None,
+              n_bins: int = 10, word_start=None) -> dict:
+    """Are the word confidences calibrated, and at which softmax temperature are they best?  recordings: (id, spec (1, F, T),
+    gold_text) triples as `evaluate` takes them.  Each recording is decoded once (greedy); ONE launch of the temperature sweep gives
+    its frame confidences at all `temperatures`, the aggregation of `confidence` makes token and word confidences of every row, and
+    the edit alignment of the hypothesis words against the reference words (both through `normalize` and lower(); all recordings
+    in one launch) labels every hypothesis word correct (a hit) or wrong (substituted or inserted).  A word that `normalize` cuts
+    into several carries its confidence to each piece; one that it deletes drops out.  The words of all recordings are pooled.
+    Returns {'temperatures', 'metrics': decoding.calibration.calibration_metrics per temperature, 'temperature': the grid point
+    fit_temperature chooses (highest NCE), 'labels': the pooled 1 / 0 labels, 'confusion_pairs': (reference word, hypothesis word,
+    count) of the substitutions, 'words': the number of pooled hypothesis words}."""
+    args = _Args() if args is None else args
+    normalize = (lambda s: s) if normalize is None else normalize
+    temperatures = [float(t) for t in temperatures]
+    blank = model.decoder.num_classes - 1
+    hyps, golds, confs = [], [], []
+    with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
+        for rec_id, spec, gold_text in recordings:
+            logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
+                             return_numpy=False)
+            words, conf = _word_confidence_sweep(logits, blank, temperatures, confidence, tokenizer, word_start)
+            pieces, source = [], []
+            for w, text in enumerate(words):
+                for piece in normalize(text).lower().split():
+                    pieces.append(piece)
+                    source.append(w)
+            hyps.append(' '.join(pieces))
+            golds.append(' '.join(normalize(gold_text).lower().split()))
+            confs.append(conf[:, torch.tensor(source, dtype=torch.long, device=conf.device)])
+    if not hyps:
+        raise ValueError('calibrate: no recordings')
+    alignments = word_error_alignment(hyps, golds)
+    labels = []
+    for hyp, ops in zip(hyps, alignments):
+        lab = [0] * len(hyp.split())
+        for o in ops:
+            if o['op'] == 'hit':
+                lab[o['hyp_index']] = 1
+        labels += lab
+    pooled = torch.cat(confs, dim=1)
+    correct = torch.tensor(labels, dtype=torch.float64)
+    metrics = [calibration_metrics(pooled[k], correct, n_bins) for k in range(len(temperatures))]
+    return {'temperatures': temperatures, 'metrics': metrics, 'temperature': fit_temperature(None, None, temperatures, metrics=metrics),
+            'labels': labels, 'confusion_pairs': confusion_pairs(alignments), 'words': len(labels)}
 
 
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR, corrupt=None):

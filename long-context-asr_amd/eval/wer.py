@@ -13,11 +13,12 @@ every alignment has ins - del = len(hyp) - len(ref) and sub + del + ins = errors
 token, inner spaces included); `words` counts len(list(reference)) exactly as the reference function does."""
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from .. import functional as Fn          # Fn.ops: the HIP op layer (tests swap it for the CPU kernel references)
+from ..hip import calib as calib_kernels  # the alignment kernel (tests swap its ops for the numpy restatement)
 
 
 def _device():
@@ -71,6 +72,94 @@ def word_error_rate_detail(hypotheses: List[str], references: List[str], use_cer
     errors, subs, dels, ins = (int(v) for v in edit_counts_of_ids(hyps, refs).sum(0))
     assert errors == subs + dels + ins
     return 1.0 * errors / words, words, 1.0 * ins / words, 1.0 * dels / words, 1.0 * subs / words
+
+
+def _tokens(h: str, r: str, use_cer: bool) -> Tuple[list, list]:
+    """The tokens of one pair, exactly as word_error_rate_detail cuts them."""
+    if use_cer:
+        return (list(h.strip()), list(r.strip())) if len(list(r)) != 0 else (list(h), [])
+    return h.split(), r.split()
+
+
+def edit_alignment_on_device(hyps: Sequence[Sequence[int]], refs: Sequence[Sequence[int]]):
+    """P pairs of id lists -> (hyp, hyp_off, ref, ref_off, hyp_to_ref, ref_to_hyp, counts), flat tensors on the device as
+    include/sconf_calib.h lays them out: one upload, one launch of the alignment kernel (csrc/calib.hip), nothing read back.  Every
+    pair's slice of the workspace is sized from the host lengths, so no pair comes back refused."""
+    if len(hyps) != len(refs):
+        raise ValueError(f'need as many hypotheses as references, got {len(hyps)} and {len(refs)}')
+    dev = _device()
+    h, ho = _ragged(hyps, dev)
+    r, ro = _ragged(refs, dev)
+    off = calib_kernels.workspace_offsets([len(s) for s in hyps], [len(s) for s in refs])
+    ws = torch.empty(off[-1], dtype=torch.uint8, device=dev) if off[-1] else None
+    h2r, r2h, counts = calib_kernels.edit_align(h, ho, r, ro, torch.tensor(off, dtype=torch.int64).to(dev), ws)
+    return h, ho, r, ro, h2r, r2h, counts
+
+
+def edit_alignment_of_ids(hyps: Sequence[Sequence[int]], refs: Sequence[Sequence[int]]) -> List[Tuple[List[int], List[int], List[int]]]:
+    """Per pair (hyp_to_ref, ref_to_hyp, counts) on the host: for every hypothesis id the index of the reference id it is aligned to
+    (-1: an insertion), for every reference id the index of its hypothesis id (-1: a deletion), and [errors, substitutions,
+    deletions, insertions] as edit_counts_of_ids gives them.  The alignment is the unique one of include/sconf_calib.h: fewest
+    errors, among those fewest substitutions, among those the backtrace's order diagonal, up, left."""
+    if len(hyps) == 0 and len(refs) == 0:
+        return []
+    _, _, _, _, h2r, r2h, counts = edit_alignment_on_device(hyps, refs)
+    h2r, r2h, counts = h2r.cpu().tolist(), r2h.cpu().tolist(), counts.cpu().tolist()
+    out, a, b = [], 0, 0
+    for p, (hs, rs) in enumerate(zip(hyps, refs)):
+        out.append((h2r[a:a + len(hs)], r2h[b:b + len(rs)], counts[p]))
+        a, b = a + len(hs), b + len(rs)
+    return out
+
+
+def word_error_alignment(hypotheses: List[str], references: List[str], use_cer=False) -> List[List[dict]]:
+    """The error listing behind word_error_rate_detail: per pair a list of {'op': 'hit' | 'sub' | 'ins' | 'del', 'hyp', 'ref',
+    'hyp_index', 'ref_index'} (the word and its position on each side, None on the side an insertion or a deletion lacks), in
+    reference order with every insertion placed before the next aligned reference word.  Tokens are cut exactly as
+    word_error_rate_detail cuts them; all pairs are aligned by one launch (edit_alignment_of_ids)."""
+    if len(hypotheses) != len(references):
+        raise ValueError(f'need as many hypotheses as references, got {len(hypotheses)} and {len(references)}')
+    ids: dict = {}
+    words, hyps, refs = [], [], []
+    for h, r in zip(hypotheses, references):
+        h_list, r_list = _tokens(h, r, use_cer)
+        words.append((h_list, r_list))
+        hyps.append([ids.setdefault(t, len(ids)) for t in h_list])
+        refs.append([ids.setdefault(t, len(ids)) for t in r_list])
+    out = []
+    for (h_list, r_list), (h2r, r2h, _) in zip(words, edit_alignment_of_ids(hyps, refs)):
+        ops, i = [], 0
+
+        def insertions(upto):
+            nonlocal i
+            while i < upto:
+                if h2r[i] < 0:
+                    ops.append({'op': 'ins', 'hyp': h_list[i], 'ref': None, 'hyp_index': i, 'ref_index': None})
+                i += 1
+
+        for j, a in enumerate(r2h):
+            if a < 0:
+                ops.append({'op': 'del', 'hyp': None, 'ref': r_list[j], 'hyp_index': None, 'ref_index': j})
+                continue
+            insertions(a)
+            ops.append({'op': 'hit' if h_list[a] == r_list[j] else 'sub', 'hyp': h_list[a], 'ref': r_list[j], 'hyp_index': a, 'ref_index': j})
+            i = a + 1
+        insertions(len(h_list))
+        out.append(ops)
+    return out
+
+
+def confusion_pairs(alignments, references: Optional[List[str]] = None, use_cer=False) -> List[Tuple[str, str, int]]:
+    """(reference word, hypothesis word, count) of every substitution, sorted by falling count and then by the two words.
+    alignments: what word_error_alignment returns - or, with `references`, the hypotheses it takes."""
+    if references is not None:
+        alignments = word_error_alignment(alignments, references, use_cer)
+    tally: dict = {}
+    for ops in alignments:
+        for o in ops:
+            if o['op'] == 'sub':
+                tally[(o['ref'], o['hyp'])] = tally.get((o['ref'], o['hyp']), 0) + 1
+    return sorted(((r, h, n) for (r, h), n in tally.items()), key=lambda t: (-t[2], t[0], t[1]))
 
 
 def _compact(padded: torch.Tensor, lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
