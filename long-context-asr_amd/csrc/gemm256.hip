@@ -26,16 +26,24 @@
 //        (s, q2), (s, q3); B1, A1 of K-tile s+1 in (s, q0), (s, q1); read phases: A0/B0 q0, B1 q1, A1 q2 - always >= 5
 //        phases after the issue.
 //   DMA issue (dma_voff, Cursor below): `buffer_load_dwordx4 ... offen lds` from inline asm (gfx950.h dma_pieces / dma_piece), one
-//        statement per half-tile.  Per lane ONE loop-invariant 32-bit offset per operand; the descriptor (based at the K-tile's corner
-//        of the operand, num_records = what the operand has left from there), the piece / half steps and the LDS destination (M0) are
-//        scalar.  What the asm form changes for the hazards above: nothing in the ORDER - the statements clobber "memory", so the
+//        statement per half-tile.  Per lane ONE loop-invariant 32-bit offset per operand; the descriptor (one per operand and work
+//        ITEM, based at the item's corner of the operand, num_records = what the operand has left from there), the K-tile's offset
+//        from that corner, the piece / half steps on top of it and the LDS destination (M0) are scalar: a K-tile step is one scalar
+//        add per operand and one subtraction for the LDS slot.  What the asm form changes for the hazards above: nothing in the ORDER - the statements clobber "memory", so the
 //        compiler moves no LDS read and no epilogue load or store across an issue or a wait, and every issue sits where the builtin
 //        sat - but the compiler no longer counts these loads: vmcnt is in order and shared, the loop holds no vector-memory
 //        operation of the compiler's own, and the epilogue's loads are issued after the item's last DMA, so a wait the compiler
 //        emits for them also retires the older DMA (it over-waits, never under-waits).  M0 is saved and restored inside each
 //        statement; SCC is named as clobbered.
+//   Steady loop and tail (ktile in the kernels): the ORDER of issues, waits, barriers, reads and MFMAs above is that of every K-tile;
+//        the K-tile exists in two forms that differ only in what surrounds the issues.  A K-tile whose prefetch cursor, two K-tiles
+//        ahead, stays inside ITS work item is known to issue all four half-tiles through descriptors that are already built: the
+//        steady form has no validity test, a constant vmcnt window, Cursor::step as its advance, and the issue forms without the
+//        leading s_nop 4 (its listing holds no VALU write of an SGPR, and 24 LDS reads lie between its entry and the first issue).
+//        The run lengths are scalar and known at each crossing; after each run comes ONE K-tile in the general form, in which
+//        the cursor crosses into its next item (item_coords' divisions, two 64-bit products, two descriptors) or runs out:
 //   Tail  past the workgroup's last item the cursor is invalid: nothing is issued and the wait drains (vmcnt(0)).  The test is one
-//        scalar compare and branch per phase.  (A zero-record descriptor would turn the issue into a no-op with the same vmcnt
+//        scalar compare and branch per phase of the general form.  (A zero-record descriptor would turn the issue into a no-op with the same vmcnt
 //        accounting, but it writes zeros through the LDS-DMA path into the next K-tile's images while the other wave row may still
 //        be two barriers behind: safe by the WAR rule above, yet it buys one branch and costs 8 zero-fill pieces per K-tile of the
 //        tail - not taken.)
@@ -44,6 +52,7 @@
 #endif
 #include "gemm_tile.h"
 #include <algorithm>
+#include <type_traits>
 #include <stdio.h>
 
 namespace {
@@ -184,42 +193,72 @@ __device__ __forceinline__ Item item_coords(const GemmParams& p, const Sched& sc
     w.nkt = (min(p.K, w.kbeg + p.k_per_split) - w.kbeg) / TK;
     return w;
 }
-// One past the last byte of each operand and the K-tile steps of the prefetch stream (wave-uniform, set once per launch).
+// One past the last byte of each operand, the K-tile steps of the prefetch stream and the sum of the wave's two LDS slots
+// (wave-uniform, set once per launch).
 template <bool KS> struct DmaGeom {
-    const char* aend; const char* bend; long astep, bstep;
-    __device__ __forceinline__ void set(const GemmParams& p) {
+    const char* aend; const char* bend; unsigned astep, bstep, ldsum;
+    __device__ __forceinline__ void set(const GemmParams& p, unsigned ldsw) {
         aend = reinterpret_cast<const char*>(p.A) + (KS ? (long)(p.K - 1) * p.lda + p.M : (long)(p.M - 1) * p.lda + p.K) * 2;
         bend = reinterpret_cast<const char*>(p.B) + (KS ? (long)(p.K - 1) * p.ldb + p.N : (long)(p.N - 1) * p.ldb + p.K) * 2;
-        astep = KS ? TK * p.lda * 2 : TK * 2; bstep = KS ? TK * p.ldb * 2 : TK * 2;
-    }
-};
-// Position in the workgroup's stream of K-tiles (all wave-uniform, i.e. SGPRs; `valid` is an int so that it is tested as a scalar, not
-// as a lane mask).  pa / pb point at the K-tile's corner of each operand: the bases of the buffer descriptors the DMA is issued
-// through, whose num_records is what the operand has left from there (an indexing error reads zeros, not memory past the tensor).
-// They are REBASED with 64-bit arithmetic, per work item by seek() (the stream's only multiplies) and per K-tile by a scalar add in
-// advance(), so that what is left for the 32-bit offset fields is one pair of half-tiles: operands of any size, and K-strided items
-// whose k-range times ld passes 4 GiB, stay on this kernel.
-template <bool KS> struct Cursor {
-    int v, kt, par, valid; Item it;
-    const char* pa; const char* pb;
-    __device__ __forceinline__ void seek(const GemmParams& p) {
-        pa = reinterpret_cast<const char*>(p.A) + (KS ? (long)it.kbeg * p.lda + it.m0 : (long)it.m0 * p.lda + it.kbeg) * 2;
-        pb = reinterpret_cast<const char*>(p.B) + (KS ? (long)it.kbeg * p.ldb + it.n0 : (long)it.n0 * p.ldb + it.kbeg) * 2;
-    }
-    __device__ __forceinline__ void advance(const GemmParams& p, const Sched& sc, const DmaGeom<KS>& g) {
-        par ^= 1;
-        if (++kt < it.nkt) { pa += g.astep; pb += g.bstep; return; }
-        kt = 0; v += gridDim.x;
-        if (v < sc.total) { it = item_coords(p, sc, v); seek(p); } else valid = 0;
+        astep = KS ? (unsigned)(TK * p.lda * 2) : TK * 2; bstep = KS ? (unsigned)(TK * p.ldb * 2) : TK * 2;   // (not used by far launches)
+        ldsum = 2 * ldsw + BUF;
     }
 };
 // descriptor over [base, end), num_records clamped to 4 GiB - 1 by the high word of the distance.  The high word passes through
-// tie_s: written as a plain 64-bit comparison it becomes v_cmp_lt_u64 (there is no scalar one) - two VALU instructions per issue.
+// tie_s: written as a plain 64-bit comparison it becomes v_cmp_lt_u64 (there is no scalar one) - two VALU instructions per descriptor.
 __device__ __forceinline__ srd_t dma_srd(const char* base, const char* end) {
     const unsigned long left = (unsigned long)(end - base);
     const unsigned hi = tie_s((unsigned)(left >> 32));
     return make_srd_uniform(base, hi ? 0xffffffffL : (long)(unsigned)left);
 }
+// Position in the workgroup's stream of K-tiles (all wave-uniform, i.e. SGPRs; `valid` is an int so that it is tested as a scalar, not
+// as a lane mask).  The DMA is issued through ONE buffer descriptor per operand and work item, da / db, built by seek() (the stream's
+// only multiplies) and based at the ITEM's corner of the operand.  The prefetch runs into the next item while the current one is
+// still being computed, so the descriptors belong to the cursor.  Inside an item a K-tile step is one scalar add on the operand's
+// offset from that corner, oa / ob (K-contiguous: the same 128 bytes for both, kept once), which goes into the instruction's scalar
+// offset with the half and piece steps on top; `lds` is the wave's slot in the buffer the K-tile lands in, flipped by one subtraction.
+// num_records is what the operand has left from the item's corner, and the range check takes the scalar offset in (a descriptor
+// shortened by the item's K-tile steps reads zeros for the last rows of the operand's last tile - measured): an indexing error in
+// any part of the offset reads zeros, never memory past the tensor - the guarantee the per-K-tile descriptors gave.
+// FAR launches (far_launch below, decided on the host; an instantiation of their own): an item's offsets do not fit 32 bits.  There
+// pa / pb follow the K-TILE's corner with 64-bit adds, the descriptors are rebuilt from them per K-tile and oa / ob stay 0 - paid by
+// those launches only: operands of any size, and K-strided items whose k-range times ld passes 4 GiB, stay on this kernel.
+// step() is advance() for a K-tile that is known to stay inside the cursor's item of a launch that is not far: no test, no branch; it
+// leaves kt to the caller, who adds a whole run of steps at once.
+template <bool KS, bool FAR> struct Cursor {
+    int v, kt, valid; Item it;
+    unsigned lds, oa, ob;
+    srd_t da, db;
+    const char* pa; const char* pb;                                   // FAR only
+    __device__ __forceinline__ unsigned offb() const { return KS ? ob : oa; }
+    __device__ __forceinline__ void seek(const GemmParams& p, const DmaGeom<KS>& g) {
+        const char* ca = reinterpret_cast<const char*>(p.A) + (KS ? (long)it.kbeg * p.lda + it.m0 : (long)it.m0 * p.lda + it.kbeg) * 2;
+        const char* cb = reinterpret_cast<const char*>(p.B) + (KS ? (long)it.kbeg * p.ldb + it.n0 : (long)it.n0 * p.ldb + it.kbeg) * 2;
+        da = dma_srd(ca, g.aend); db = dma_srd(cb, g.bend);
+        oa = 0; ob = 0;
+        if (FAR) { pa = ca; pb = cb; }
+    }
+    __device__ __forceinline__ void step(const DmaGeom<KS>& g) {
+        lds = g.ldsum - lds;
+        oa += g.astep;
+        if (KS) ob += g.bstep;
+    }
+    __device__ __forceinline__ void advance(const GemmParams& p, const Sched& sc, const DmaGeom<KS>& g) {
+        lds = g.ldsum - lds;
+        if (++kt < it.nkt) {
+            if (!FAR) { oa += g.astep; if (KS) ob += g.bstep; }
+            else {
+                pa += (KS ? (long)TK * p.lda * 2 : (long)TK * 2); pb += (KS ? (long)TK * p.ldb * 2 : (long)TK * 2);
+                da = dma_srd(pa, g.aend); db = dma_srd(pb, g.bend);
+            }
+            return;
+        }
+        kt = 0; v += gridDim.x;
+        if (v < sc.total) { it = item_coords(p, sc, v); seek(p, g); } else valid = 0;
+    }
+    // how many step()s may follow from here: K-tiles left in the cursor's item after this one
+    __device__ __forceinline__ int run() const { return valid && !FAR ? it.nkt - 1 - kt : 0; }
+};
 
 // Epilogue of one work item for one wave (ACT and the presence of a residual fixed at compile time).  All loads are issued
 // before the stores they could queue behind: the bias run once, the aux tile (bf16) per half of 4 row blocks, the residual
@@ -492,13 +531,15 @@ __device__ unsigned long long g_gemm_stamps[256 * 8 * 8];
 #define STAMP_OUT
 #endif
 // leave the 4 youngest half-tiles in flight: 2 + 2 + 2 + JH DMA instructions per wave
+constexpr std::true_type STEADY{};                 // tags of the two K-tile forms (ktile in the kernels)
+constexpr std::false_type TAIL{};
 template <int JH> __device__ __forceinline__ void wait_window(bool streaming) {
     if (!streaming) wait_vm<0>();
     else if (JH == 2) wait_vm<8>();
     else wait_vm<7>();
 }
 
-template <bool KS, int EK = -1>
+template <bool KS, int EK = -1, bool FAR = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     constexpr int JH = 2, TN = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][A0 | A1 | B0 | B1], 128 KiB: the ONLY LDS object
@@ -514,17 +555,17 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     const bool rotb = !KS && p.rot_cos != nullptr;
     const unsigned va = dma_voff<KS, false, JH>(p.lda, tid), vb = dma_voff<KS, true, JH>(p.ldb, tid, rotb);
     DmaSteps<KS, false, JH> sa; DmaSteps<KS, true, JH> sb; sa.set(p.lda); sb.set(p.ldb, rotb);
-    DmaGeom<KS> geo; geo.set(p);
     const unsigned ldsw = lds_addr(smem) + wave * 1024;
-    // the wave's slot in buffer `par`; the image offset is added as a literal at the issue (tie_s: else the compiler hoists one sum per image)
-    auto lds_buf = [&](int par) { return tie_s(ldsw + par * BUF); };
-    auto issue_a = [&](const Cursor<KS>& c, int h) {
-        if (!c.valid) return;
-        dma_pieces<2, 8192>(dma_srd(c.pa, geo.aend), va, h * sa.half(), sa.piece, lds_buf(c.par) + h * HT);
+    DmaGeom<KS> geo; geo.set(p, ldsw);
+    // one half-tile through the cursor's descriptor; the image offset is added to the wave's slot as a literal at the issue (tie_s: else
+    // the compiler hoists one sum per image).  steady (the K-tiles of the steady loop below): the cursor is known valid - no test.
+    auto issue_a = [&](const Cursor<KS, FAR>& c, int h, auto steady) __attribute__((always_inline)) {
+        if constexpr (decltype(steady)::value) dma_pieces_s<2, 8192>(c.da, va, c.oa + h * sa.half(), sa.piece, tie_s(c.lds) + h * HT);
+        else if (c.valid) dma_pieces<2, 8192>(c.da, va, c.oa + h * sa.half(), sa.piece, tie_s(c.lds) + h * HT);
     };
-    auto issue_b = [&](const Cursor<KS>& c, int h) {
-        if (!c.valid) return;
-        dma_pieces<2, 8192>(dma_srd(c.pb, geo.bend), vb, h * sb.half(), sb.piece, lds_buf(c.par) + (2 + h) * HT);
+    auto issue_b = [&](const Cursor<KS, FAR>& c, int h, auto steady) __attribute__((always_inline)) {
+        if constexpr (decltype(steady)::value) dma_pieces_s<2, 8192>(c.db, vb, c.offb() + h * sb.half(), sb.piece, tie_s(c.lds) + (2 + h) * HT);
+        else if (c.valid) dma_pieces<2, 8192>(c.db, vb, c.offb() + h * sb.half(), sb.piece, tie_s(c.lds) + (2 + h) * HT);
     };
 
     f32x4 acc[2][4][2 + JH];
@@ -535,13 +576,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 2 + JH; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    Cursor<KS> pc;                                    // prefetch cursor
-    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p);
+    Cursor<KS, FAR> pc;                               // prefetch cursor
+    pc.v = blockIdx.x; pc.kt = 0; pc.lds = ldsw; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p, geo);
     int cv = pc.v; Item cit = pc.it;                  // compute position
     // prologue: K-tile 0 entirely, A0/B0 of K-tile 1 (the "phases -6 .. -1" of the schedule)
-    issue_a(pc, 0); issue_b(pc, 0); issue_b(pc, 1); issue_a(pc, 1);
+    issue_a(pc, 0, TAIL); issue_b(pc, 0, TAIL); issue_b(pc, 1, TAIL); issue_a(pc, 1, TAIL);
     pc.advance(p, sc, geo);
-    issue_a(pc, 0); issue_b(pc, 0);
+    issue_a(pc, 0, TAIL); issue_b(pc, 0, TAIL);
     if (pc.valid) wait_window<JH>(true);             // A0, B0 of K-tile 0 have landed
     else wait_vm<4>();
     __builtin_amdgcn_s_barrier();
@@ -551,9 +592,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
     STAMP_DECL(8)
     while (true) {
         if (wr) __builtin_amdgcn_s_barrier();         // stagger the second wave row by one barrier
-        for (int kt = 0; kt < cit.nkt; ++kt) {
+        // One K-tile.  steady: every issue of it is known valid and its advance stays inside the cursor's item (Cursor::step) - no
+        // validity test, no drain, no item crossing; otherwise the general form with all of them.
+        auto ktile = [&](auto steady, const bool last) __attribute__((always_inline)) {
+            constexpr bool ST = decltype(steady)::value;
             const char* buf = smem + cur * BUF;
-            const bool last = kt == cit.nkt - 1;
             // ---- q0: B-lo, A-lo -> acc[0][.][0..1] ---------------------------------------------------------------
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -572,9 +615,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                 }
             }
             STAMP(6);
-            issue_b(pc, 1);
+            issue_b(pc, 1, steady);
             STAMP(7);
-            wait_window<JH>(pc.valid);
+            wait_window<JH>(ST || pc.valid);
             STAMP(0);
             __builtin_amdgcn_s_barrier();
             STAMP(1);
@@ -610,9 +653,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                 }
             }
             STAMP(6);
-            issue_a(pc, 1);
+            issue_a(pc, 1, steady);
             STAMP(7);
-            wait_window<JH>(pc.valid);
+            wait_window<JH>(ST || pc.valid);
             STAMP(0);
             __builtin_amdgcn_s_barrier();
             STAMP(1);
@@ -644,11 +687,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
                     for (int kk = 0; kk < 2; ++kk) fa[i][kk] = frag_a<KS>(buf + HT, wr, i, kk, lane);
                 }
             }
-            pc.advance(p, sc, geo);
+            if constexpr (ST) pc.step(geo); else pc.advance(p, sc, geo);
             STAMP(6);
-            issue_a(pc, 0);
+            issue_a(pc, 0, steady);
             STAMP(7);
-            wait_window<JH>(pc.valid);
+            wait_window<JH>(ST || pc.valid);
             STAMP(0);
             __builtin_amdgcn_s_barrier();
             STAMP(1);
@@ -673,9 +716,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
             STAMP(3);
             // ---- q3: (B-lo still in registers) -> acc[1][.][0..1] ------------------------------------------------
             STAMP(6);
-            issue_b(pc, 0);
+            issue_b(pc, 0, steady);
             STAMP(7);
-            wait_window<JH>(pc.valid);
+            wait_window<JH>(ST || pc.valid);
             STAMP(0);
             __builtin_amdgcn_s_barrier();
             STAMP(1);
@@ -692,6 +735,14 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
             if (!(wr && last)) __builtin_amdgcn_s_barrier();   // the lagging row goes straight into its epilogue
             STAMP(3);
             cur ^= 1;
+        };
+        // The stream of this item's K-tiles: runs of steady K-tiles - as many as the cursor, two K-tiles ahead, has left in ITS item -
+        // each followed by one general K-tile, in which the cursor crosses into its next item or runs out (far launches: all general).
+        for (int kt = 0; kt < cit.nkt;) {
+            const int run = min(cit.nkt - kt, pc.run());
+            pc.kt += run;
+            for (const int kend = kt + run; kt < kend; ++kt) ktile(STEADY, kt == cit.nkt - 1);
+            if (kt < cit.nkt) { ktile(TAIL, kt == cit.nkt - 1); ++kt; }
         }
         // ---- epilogue: both wave rows concurrently; one specialised, contiguous code path per (activation, residual) ------
         if constexpr (KS) epilogue256<SCONF_ACT_NONE, false, true, JH>(p, acc, cit, wr, wc, lane);
@@ -741,18 +792,21 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
     const unsigned va = dma_voff<KS, false, JH>(p.lda, tid), vb = dma_voff<KS, true, JH>(p.ldb, tid);
     const unsigned vb1 = dma_voff<KS, true, JH>(p.ldb, tid, false, true);          // the 64-row B1 image: own row map and swizzle
     DmaSteps<KS, false, JH> sa; DmaSteps<KS, true, JH> sb; sa.set(p.lda); sb.set(p.ldb);
-    DmaGeom<KS> geo; geo.set(p);
     const unsigned ldsw = lds_addr(smem) + wave * 1024;
-    // the wave's slot in buffer `par`; the image offset is added as a literal at the issue (tie_s: else the compiler hoists one sum per image)
-    auto lds_buf = [&](int par) { return tie_s(ldsw + par * BUF); };
-    auto issue_a = [&](const Cursor<KS>& c, int h) {
-        if (!c.valid) return;
-        dma_pieces<2, 8192>(dma_srd(c.pa, geo.aend), va, h * sa.half(), sa.piece, lds_buf(c.par) + h * HT);
+    DmaGeom<KS> geo; geo.set(p, ldsw);
+    // one half-tile through the cursor's descriptor (gemm256_kernel has the notes); B1 is a single piece with its own per-lane offset
+    auto issue_a = [&](const Cursor<KS, false>& c, int h, auto steady) __attribute__((always_inline)) {
+        if constexpr (decltype(steady)::value) dma_pieces_s<2, 8192>(c.da, va, c.oa + h * sa.half(), sa.piece, tie_s(c.lds) + h * HT);
+        else if (c.valid) dma_pieces<2, 8192>(c.da, va, c.oa + h * sa.half(), sa.piece, tie_s(c.lds) + h * HT);
     };
-    auto issue_b = [&](const Cursor<KS>& c, int h) {
-        if (!c.valid) return;
-        if (h == 0) dma_pieces<2, 8192>(dma_srd(c.pb, geo.bend), vb, 0, sb.piece, lds_buf(c.par) + 2 * HT);
-        else        dma_piece(dma_srd(c.pb, geo.bend), vb1, 0, lds_buf(c.par) + 3 * HT);
+    auto issue_b = [&](const Cursor<KS, false>& c, int h, auto steady) __attribute__((always_inline)) {
+        if constexpr (decltype(steady)::value) {
+            if (h == 0) dma_pieces_s<2, 8192>(c.db, vb, c.oa, sb.piece, tie_s(c.lds) + 2 * HT);
+            else        dma_piece_s(c.db, vb1, c.oa, tie_s(c.lds) + 3 * HT);
+        } else if (c.valid) {
+            if (h == 0) dma_pieces<2, 8192>(c.db, vb, c.oa, sb.piece, tie_s(c.lds) + 2 * HT);
+            else        dma_piece(c.db, vb1, c.oa, tie_s(c.lds) + 3 * HT);
+        }
     };
 
     f32x4 acc[2][4][3];
@@ -763,13 +817,13 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    Cursor<KS> pc;                                    // prefetch cursor: the K-tile whose A0/B0 were issued last
-    pc.v = blockIdx.x; pc.kt = 0; pc.par = 0; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p);
+    Cursor<KS, false> pc;                             // prefetch cursor: the K-tile whose A0/B0 were issued last
+    pc.v = blockIdx.x; pc.kt = 0; pc.lds = ldsw; pc.valid = 1; pc.it = item_coords(p, sc, pc.v); pc.seek(p, geo);
     int cv = pc.v; Item cit = pc.it;
     // prologue: K-tile 0 entirely, A0/B0 of K-tile 1
-    issue_a(pc, 0); issue_b(pc, 0); issue_a(pc, 1); issue_b(pc, 1);
+    issue_a(pc, 0, TAIL); issue_b(pc, 0, TAIL); issue_a(pc, 1, TAIL); issue_b(pc, 1, TAIL);
     pc.advance(p, sc, geo);
-    issue_a(pc, 0); issue_b(pc, 0);
+    issue_a(pc, 0, TAIL); issue_b(pc, 0, TAIL);
     if (pc.valid) wait_vm<7>(); else wait_vm<3>();           // A0, B0 of K-tile 0 have landed
     __builtin_amdgcn_s_barrier();
 
@@ -777,9 +831,11 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
     bf16x8 flo[4][2], fhi[4][2], blo[2][2], bhi[2];
     while (true) {
         if (wr) __builtin_amdgcn_s_barrier();         // stagger the second wave row by one barrier
-        for (int kt = 0; kt < cit.nkt; ++kt) {
+        // One K-tile.  steady: every issue of it is known valid and its advance stays inside the cursor's item (Cursor::step) - no
+        // validity test, no drain, no item crossing; otherwise the general form with all of them.
+        auto ktile = [&](auto steady, const bool last) __attribute__((always_inline)) {
+            constexpr bool ST = decltype(steady)::value;
             const char* buf = smem + cur * BUF;
-            const bool last = kt == cit.nkt - 1;
             // ---- P0 ------------------------------------------------------------------------------------------------
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -789,8 +845,8 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) flo[i][kk] = frag_a<false>(buf, wr, i, kk, lane);
-            issue_a(pc, 1); issue_b(pc, 1);             // pc = K-tile s+1
-            wait_window<JH>(pc.valid);
+            issue_a(pc, 1, steady); issue_b(pc, 1, steady);             // pc = K-tile s+1
+            wait_window<JH>(ST || pc.valid);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -821,9 +877,9 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_s_barrier();
             // ---- P2 ------------------------------------------------------------------------------------------------
-            pc.advance(p, sc, geo);                          // pc = K-tile s+2
-            issue_a(pc, 0); issue_b(pc, 0);
-            wait_window<JH>(pc.valid);
+            if constexpr (ST) pc.step(geo); else pc.advance(p, sc, geo);   // pc = K-tile s+2
+            issue_a(pc, 0, steady); issue_b(pc, 0, steady);
+            wait_window<JH>(ST || pc.valid);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -836,6 +892,14 @@ __global__ __launch_bounds__(512) void gemm192_kernel(const GemmParams p) {
             __builtin_amdgcn_s_setprio(0);
             if (!(wr && last)) __builtin_amdgcn_s_barrier();   // the lagging row goes straight into its epilogue
             cur ^= 1;
+        };
+        // The stream of this item's K-tiles: runs of steady K-tiles - as many as the cursor, two K-tiles ahead, has left in ITS item -
+        // each followed by one general K-tile, in which the cursor crosses into its next item or runs out (far launches: all general).
+        for (int kt = 0; kt < cit.nkt;) {
+            const int run = min(cit.nkt - kt, pc.run());
+            pc.kt += run;
+            for (const int kend = kt + run; kt < kend; ++kt) ktile(STEADY, kt == cit.nkt - 1);
+            if (kt < cit.nkt) { ktile(TAIL, kt == cit.nkt - 1); ++kt; }
         }
         if constexpr (EK >= 0) EPILOGUE_ONE(EK, JH);
         else EPILOGUE_NT(JH);
@@ -869,6 +933,13 @@ static int pick_width(const GemmParams& p, int layout, int cus) {
     return bw;
 }
 
+// K-strided launches whose per-item offsets do not fit the 32-bit offset fields of the LDS-DMA (Cursor): the last K-tile of an item
+// starts (k - 64) ld elements from the item's corner, its second piece 32 ld further, and a lane's own offset is at most 63 ld + 256 -
+// (k + 32) ld elements and 1 KiB bound the sum.  (K-contiguous items span 2 K bytes, far below the limit that fits32 below sets.)
+static bool far_launch(const GemmParams& p) {
+    return ((long)p.k_per_split + 32) * std::max(p.lda, p.ldb) * 2 + 1024 > 0xffffffffL;
+}
+
 bool sconf_gemm256_eligible(const GemmParams& p, int layout) {
     if (layout != 0 && layout != 2) return false;
     const bool ks = layout == 2;
@@ -876,12 +947,13 @@ bool sconf_gemm256_eligible(const GemmParams& p, int layout) {
     if (ks ? (p.act != SCONF_ACT_NONE || p.resid || p.pre)
            : !(p.act == SCONF_ACT_NONE || ((p.act == SCONF_ACT_GELU_DSAVE || p.act == SCONF_ACT_MULAUX) && !p.resid) ||
                (p.act == SCONF_ACT_SMAXBWD && !p.resid && !p.bias && !p.out_f32 && !p.pre && p.splits == 1))) return false;
-    // The 32-bit offset fields of the LDS-DMA (per-lane voffset + scalar soffset, against a descriptor that the kernel rebases to
-    // the K-tile's corner of the operand with 64-bit arithmetic): the farthest 16 bytes of one K-tile's pair of half-tiles end
-    // (255 ld + 64) * 2 bytes from that corner for a K-contiguous operand (256 rows x 64 k) and (63 ld + 256) * 2 for a K-strided one
-    // (64 k-rows x 256), and num_records is at most 2^32 - 1.  Neither the operand's size nor an item's k-range enters: operands
-    // beyond 4 GiB and K-strided items whose k-range times ld passes 4 GiB stay on this kernel.
-    auto fits32 = [&](long ld) { return (ks ? 63 * ld + 256 : 255 * ld + 64) * 2 <= 0xffffffffL; };
+    // The 32-bit offset fields of the LDS-DMA (per-lane voffset + scalar soffset, against a descriptor that the kernel bases at
+    // the item's corner of the operand with 64-bit arithmetic): the farthest 16 bytes of one K-tile's pair of half-tiles end
+    // (255 ld + 64) * 2 bytes from the K-tile's corner for a K-contiguous operand (256 rows x 64 k) and (63 ld + 256) * 2 for a
+    // K-strided one (64 k-rows x 256), and num_records is at most 2^32 - 1.  An item's K-tiles add 2 K bytes at most to the former
+    // (counted below) and are far_launch's business for the latter.  The operand's size does not enter: operands beyond 4 GiB and
+    // K-strided items whose k-range times ld passes 4 GiB stay on this kernel.
+    auto fits32 = [&](long ld) { return (ks ? 63 * ld + 256 : 255 * ld + 64 + p.K) * 2 <= 0xffffffffL; };
     if (!fits32(p.lda) || !fits32(p.ldb)) return false;
     const int cus = num_cus();
     const int w = pick_width(p, layout, cus);
@@ -895,7 +967,7 @@ int sconf_gemm256_width(const GemmParams& p, int layout) { return pick_width(p, 
 int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
     static bool attr_set = false;
     const size_t shmem = 2 * BUF;
-    lds_limit_once(attr_set, {(const void*)gemm256_kernel<false>, (const void*)gemm256_kernel<true>,
+    lds_limit_once(attr_set, {(const void*)gemm256_kernel<false>, (const void*)gemm256_kernel<true>, (const void*)gemm256_kernel<true, -1, true>,
                              (const void*)gemm256_kernel<false, 0>, (const void*)gemm256_kernel<false, 1>, (const void*)gemm256_kernel<false, 2>,
                              (const void*)gemm256_kernel<false, 3>, (const void*)gemm256_kernel<false, 4>, (const void*)gemm256_kernel<false, 5>,
                              (const void*)gemm256_kernel<false, 7>, (const void*)gemm256_kernel<false, 8>, (const void*)gemm256_kernel<false, 9>,
@@ -911,7 +983,10 @@ int sconf_gemm256_launch(const GemmParams& p, int layout, hipStream_t stream) {
     const int ek = layout == 2 ? -1 : epilogue_kind(p);
 #define L256(EK_) hipLaunchKernelGGL((gemm256_kernel<false, EK_>), grid, block, shmem, stream, p)
 #define L192(EK_) hipLaunchKernelGGL(gemm192_kernel<EK_>, grid, block, shmem, stream, p)
-    if (layout == 2)   hipLaunchKernelGGL((gemm256_kernel<true>), grid, block, shmem, stream, p);
+    if (layout == 2) {
+        if (far_launch(p)) hipLaunchKernelGGL((gemm256_kernel<true, -1, true>), grid, block, shmem, stream, p);
+        else               hipLaunchKernelGGL((gemm256_kernel<true>), grid, block, shmem, stream, p);
+    }
     else if (w == 256) {
         switch (ek) {
             case 0: L256(0); break; case 1: L256(1); break; case 2: L256(2); break; case 3: L256(3); break; case 4: L256(4); break;

@@ -87,7 +87,8 @@ __device__ __forceinline__ void dma_dword(srd_t srd, unsigned voff, unsigned sof
                  : "=&s"(keep), "+s"(soff), "+s"(lds_base) : "v"(voff), "s"(srd) : "memory");
 }
 // NP pieces of 16 bytes per lane: piece k reads srd base + soff + k * sstep + voff and lands at lds_wave_base + k * LSTEP + lane * 16
-#define SCONF_DMA_FIRST "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
+#define SCONF_DMA_FIRST_S "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
+#define SCONF_DMA_FIRST "s_nop 4\n\t" SCONF_DMA_FIRST_S
 #define SCONF_DMA_NEXT  "s_add_u32 m0, m0, %6\n\ts_add_u32 %1, %1, %4\n\tbuffer_load_dwordx4 %2, %3, %1 offen lds\n\t"
 #define SCONF_DMA_LAST  "s_mov_b32 m0, %0"
 // one piece: dma_pieces' first step alone - the same s_nop 4, M0 save / set / s_nop 0 / restore; no s_add, so SCC stays untouched
@@ -108,6 +109,21 @@ template <int NP, int LSTEP> __device__ __forceinline__ void dma_pieces(srd_t sr
     else
         asm volatile(SCONF_DMA_FIRST SCONF_DMA_NEXT SCONF_DMA_LAST
                      : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
+}
+// The same two forms WITHOUT the leading `s_nop 4`, for a caller whose descriptor, soff and LDS base are all written by the SALU (an
+// SALU write of an SGPR needs no wait state before a VMEM read of it) on EVERY path that reaches the statement: no v_readfirstlane,
+// no v_readlane reload of a spilled SGPR within 5 wait states ahead of it.  That is a property of the caller's compiled code, to be
+// read off its listing (gemm256.hip: the steady K-tile loops); where it is not established, use the forms above.
+__device__ __forceinline__ void dma_piece_s(srd_t srd, unsigned voff, unsigned soff, unsigned lds_wave_base) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(srd), "s"(soff), "s"(lds_wave_base) : "memory");
+}
+template <int NP, int LSTEP> __device__ __forceinline__ void dma_pieces_s(srd_t srd, unsigned voff, unsigned soff, unsigned sstep, unsigned lds_wave_base) {
+    static_assert(NP == 2, "half-tiles of 2 pieces per wave");
+    unsigned keep;
+    asm volatile(SCONF_DMA_FIRST_S SCONF_DMA_NEXT SCONF_DMA_LAST
+                 : "=&s"(keep), "+s"(soff) : "v"(voff), "s"(srd), "s"(sstep), "s"(lds_wave_base), "n"(LSTEP) : "memory", "scc");
 }
 
 // ---- in-kernel time stamps (cdna_hip_programming.md section 7) ---------------------------------------------------------
