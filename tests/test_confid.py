@@ -37,6 +37,9 @@ def lib():
 def emulated(monkeypatch):
     """The unit's three ops (lcasr_amd.hip.confid) replaced by their restatements: host logic without a GPU."""
     from lcasr_amd.decoding import confidence as K
+    # the surface moves CPU input to the device wherever one is present (confidence._on_device, calibration, wer._device, the
+    # decoders); the restatements are numpy, so the move is pinned to the CPU: the same run with and without a GPU
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     monkeypatch.setattr(K.confid_kernels, 'frames', CR.op_frames)
     monkeypatch.setattr(K.confid_kernels, 'runs', CR.op_runs)
     monkeypatch.setattr(K.confid_kernels, 'aggregate', CR.op_aggregate)
