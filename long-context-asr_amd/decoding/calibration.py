@@ -9,7 +9,8 @@ curves - are small tensor arithmetic in float64.
     idx, conf = frame_confidence_sweep(log_probs, temperatures, cfg) # conf (K, N): row k feeds token_confidence unchanged
     t = fit_temperature(conf_by_temperature, labels, temperatures)   # the grid point with the highest NCE
 
-Not part of it: posterior (forward-backward) confidences, and calibration maps other than a temperature."""
+Posterior confidences are decoding/posterior.py; eval.run.calibrate(posterior=True) scores them with calibration_metrics beside
+the measures here.  Not part of it: calibration maps other than a temperature, and n-best or lattice word posteriors."""
 from __future__ import annotations
 
 import math

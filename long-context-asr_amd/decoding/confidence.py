@@ -11,7 +11,8 @@ argmax, one collapses the argmax vector into labels with their frames, one aggre
 
 `temperature=` on frame_confidence and greedy_confidence takes the confidences of softmax(log_probs / temperature) instead (through the
 temperature sweep of csrc/calib.hip with one temperature); decoding/calibration.py holds the calibration against error labels and the
-fit of that temperature.  Not part of it: posterior (forward-backward) confidences."""
+fit of that temperature; decoding/posterior.py holds the posterior confidences, which read the CTC likelihood of the competing
+strings instead of the shape of single frames."""
 from __future__ import annotations
 
 import math

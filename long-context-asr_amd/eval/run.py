@@ -28,6 +28,7 @@ from ..decoding.calibration import calibration_metrics, fit_temperature, frame_c
 from ..decoding.confidence import (ConfidenceConfig, frame_confidence, greedy_confidence, spans_from_token_frames, token_confidence,
                                    word_confidence)
 from ..decoding.greedy import GreedyCTCDecoder
+from ..decoding.posterior import posterior_confidence_long
 from ..decoding.segment import build_targets, ctc_segment, star_id
 from ..hip import noise as noiser
 from ..utils.audio_tools import HOP_LENGTH, SR, add_background_noise, add_gaussian_snr, grab_left_channel, resample, to_spectogram
@@ -143,7 +144,7 @@ def transcribe(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: 
 def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, overlap: int, evaluation_mode: str = 'averaged_moving_window',
                       normalise: bool = True, args=None, beam_width: int = 1, lm=None, alpha: float = 0.5, beta: float = 1.5,
                       sample_rate: int = SR, corrupt=None, hotwords=None, hotword_weight: float = 10.0,
-                      confidence: ConfidenceConfig = ConfidenceConfig(), temperature: Optional[float] = None) -> dict:
+                      confidence: ConfidenceConfig = ConfidenceConfig(), temperature: Optional[float] = None, posterior: bool = False) -> dict:
     """`transcribe` with what it knows about its answer: {'text', 'tokens', 'token_confidence', 'words': [{'word', 'startTime',
     'endTime', 'confidence'}]}, the times in word_timestamps' '12.34s' form.  The keywords are transcribe's; `confidence` (a
     decoding.confidence.ConfidenceConfig) chooses the measure and the aggregations; `temperature` (what `calibrate` chose, say) takes
@@ -151,7 +152,11 @@ def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, ov
     confidence over its run of frames and the blanks behind it (without them if exclude_blank), its times from its own run.
     beam_width > 1: the best beam, the LM and the hotwords acting inside the search as in transcribe; token i covers the frames from
     its own to the next token's, a word lasts from its first token's frame to one past its last token's.  Frame, token and word
-    confidences are computed on the device (include/sconf_confid.h)."""
+    confidences are computed on the device (include/sconf_confid.h).
+    posterior=True adds what decoding.posterior knows (include/sconf_post.h; at temperature 1, for a recording of any length through
+    posterior_confidence_long with the decoded ids and their spans): 'token_posterior', the posterior of every token among the strings
+    at edit distance 1 in its slot; 'token_alternative', per token {'token': the best competing id, None for "delete", 'posterior'};
+    and a 'posterior' on every word, its tokens' posteriors through the word aggregation of `confidence`."""
     args = _Args() if args is None else args
     spec = to_spectogram(_left_at_16k(waveform, sample_rate, corrupt), global_normalisation=normalise)
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
@@ -173,7 +178,17 @@ def transcribe_detail(model, waveform: torch.Tensor, tokenizer, seq_len: int, ov
     words = word_timestamps(ids, times, tokenizer, model.subsampling.subsampling_factor * HOP_LENGTH / SR, word_start=word_start)
     for w, c in zip(words, word_confidence(ids, conf, tokenizer, confidence, word_start)):
         w['confidence'] = c
-    return {'text': tokenizer.decode(ids), 'tokens': ids, 'token_confidence': conf, 'words': words}
+    out = {'text': tokenizer.decode(ids), 'tokens': ids, 'token_confidence': conf, 'words': words}
+    if posterior:
+        pc = posterior_confidence_long(logits, ids, times, blank)
+        packed = torch.cat([pc.token_posterior.view(torch.int32), pc.alternative, pc.alternative_posterior.view(torch.int32)]).cpu()   # the one copy
+        n = len(ids)
+        out['token_posterior'] = packed[:n].view(torch.float32).tolist()
+        out['token_alternative'] = [{'token': None if a == blank else a, 'posterior': p}
+                                    for a, p in zip(packed[n:2 * n].tolist(), packed[2 * n:].view(torch.float32).tolist())]
+        for w, c in zip(words, word_confidence(ids, out['token_posterior'], tokenizer, confidence, word_start)):
+            w['posterior'] = c
+    return out
 
 
 def _word_confidence_sweep(logits: torch.Tensor, blank: int, temperatures: Sequence[float], cfg: ConfidenceConfig, tokenizer, word_start=None):
@@ -197,10 +212,22 @@ def _word_confidence_sweep(logits: torch.Tensor, blank: int, temperatures: Seque
     return [tokenizer.decode([ids[k] for k in g]) for g in groups], words.reshape(K, len(groups))
 
 
+def _word_posteriors(logits: torch.Tensor, blank: int, cfg: ConfidenceConfig, tokenizer, word_start=None) -> torch.Tensor:
+    """(words,) f32 on the device: the posterior of every greedy word of logits (N, C), its tokens' posteriors
+    (decoding.posterior.posterior_confidence_long) through cfg's word aggregation; the words are _word_confidence_sweep's."""
+    g = greedy_confidence(logits, blank, cfg)
+    if not g.tokens:
+        return torch.zeros(0, dtype=torch.float32, device=g.frame_confidence.device)
+    pc = posterior_confidence_long(logits, g.tokens, [s[:2] for s in g.spans], blank)
+    groups = _word_groups(g.tokens, tokenizer, word_start)
+    first_last = torch.tensor([[w[0], w[-1] + 1] for w in groups], dtype=torch.int32).to(pc.token_posterior.device)
+    return confidence_module.confid_kernels.aggregate(pc.token_posterior.contiguous(), first_last, cfg.words, None, 0)
+
+
 def calibrate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokenizer, seq_len: int, overlap: int,
               temperatures: Sequence[float] = (0.5, 0.67, 0.8, 1.0, 1.25, 1.5, 2.0, 3.0), confidence: ConfidenceConfig = ConfidenceConfig(),
               evaluation_mode: str = 'averaged_moving_window', normalize: Optional[Callable[[str], str]] = None, args=None,
-              n_bins: int = 10, word_start=None) -> dict:
+              n_bins: int = 10, word_start=None, posterior: bool = False) -> dict:
     """Are the word confidences calibrated, and at which softmax temperature are they best?  recordings: (id, spec (1, F, T),
     gold_text) triples as `evaluate` takes them.  Each recording is decoded once (greedy); ONE launch of the temperature sweep gives
     its frame confidences at all `temperatures`, the aggregation of `confidence` makes token and word confidences of every row, and
@@ -209,12 +236,14 @@ def calibrate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeni
     into several carries its confidence to each piece; one that it deletes drops out.  The words of all recordings are pooled.
     Returns {'temperatures', 'metrics': decoding.calibration.calibration_metrics per temperature, 'temperature': the grid point
     fit_temperature chooses (highest NCE), 'labels': the pooled 1 / 0 labels, 'confusion_pairs': (reference word, hypothesis word,
-    count) of the substitutions, 'words': the number of pooled hypothesis words}."""
+    count) of the substitutions, 'words': the number of pooled hypothesis words}.  posterior=True adds 'posterior_metrics': the
+    calibration_metrics of the pooled word posteriors (decoding.posterior, at temperature 1) against the same labels, to set
+    beside the entry of 'metrics' at temperature 1."""
     args = _Args() if args is None else args
     normalize = (lambda s: s) if normalize is None else normalize
     temperatures = [float(t) for t in temperatures]
     blank = model.decoder.num_classes - 1
-    hyps, golds, confs = [], [], []
+    hyps, golds, confs, posts = [], [], [], []
     with _evaluation_mode(model, evaluation_mode, seq_len, args) as (eval_fn, seq_len):
         for rec_id, spec, gold_text in recordings:
             logits = eval_fn(args=args, model=model, spec=spec, seq_len=seq_len, overlap=overlap, tokenizer=tokenizer, use_tqdm=False,
@@ -228,6 +257,9 @@ def calibrate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeni
             hyps.append(' '.join(pieces))
             golds.append(' '.join(normalize(gold_text).lower().split()))
             confs.append(conf[:, torch.tensor(source, dtype=torch.long, device=conf.device)])
+            if posterior:
+                wp = _word_posteriors(logits, blank, confidence, tokenizer, word_start)
+                posts.append(wp[torch.tensor(source, dtype=torch.long, device=wp.device)])
     if not hyps:
         raise ValueError('calibrate: no recordings')
     alignments = word_error_alignment(hyps, golds)
@@ -241,8 +273,11 @@ def calibrate(model, recordings: Iterable[Tuple[str, torch.Tensor, str]], tokeni
     pooled = torch.cat(confs, dim=1)
     correct = torch.tensor(labels, dtype=torch.float64)
     metrics = [calibration_metrics(pooled[k], correct, n_bins) for k in range(len(temperatures))]
-    return {'temperatures': temperatures, 'metrics': metrics, 'temperature': fit_temperature(None, None, temperatures, metrics=metrics),
-            'labels': labels, 'confusion_pairs': confusion_pairs(alignments), 'words': len(labels)}
+    out = {'temperatures': temperatures, 'metrics': metrics, 'temperature': fit_temperature(None, None, temperatures, metrics=metrics),
+           'labels': labels, 'confusion_pairs': confusion_pairs(alignments), 'words': len(labels)}
+    if posterior:
+        out['posterior_metrics'] = calibration_metrics(torch.cat(posts), correct, n_bins)
+    return out
 
 
 def spectrograms_of(recordings: Iterable[Tuple[str, torch.Tensor, str]], normalise: bool = True, sample_rate: int = SR, corrupt=None):
